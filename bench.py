@@ -2,6 +2,7 @@
 """HybridVAE train throughput (users/sec) on MI355X -- the BASELINE.json metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload syn10m|syn1m|all_beauty|appliances]
+                    [--full] [--dump-outputs DIR]
 
 One "step" = one fused train step (encoder -> reparam/KL -> projection ->
 streaming decoder + multinomial loss -> backward -> clip 5.0 -> Adam) over
@@ -14,10 +15,13 @@ region. N > 1 runs one process per GPU (torchrun), user-batch data parallel
 with the gradient exchange over RCCL (weak scaling: B users per GPU per step;
 --scaling strong splits a fixed --global-batch over the GPUs).
 
-Prints ONE JSON line on rank 0, with a live roofline for the dominant kernel
-(HIP events around its launches on the stream it runs on) and the CPU
-oracle (oracle/ref_cpu.py, a pinned restatement of the reference trainer)
-timed on this host's cores on a bounded sample.
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the K
+steps and prints the headline figures only. --full adds, after the timed
+region, a live roofline for the dominant kernel (HIP events around its
+launches on the stream it runs on) and the CPU oracle (oracle/ref_cpu.py, a
+pinned restatement of the reference trainer) timed on this host's cores on a
+bounded sample. --dump-outputs DIR writes what the last timed step left
+(losses, parameters) as DIR/<name>.npy, for comparing two builds.
 """
 from __future__ import annotations
 
@@ -30,6 +34,7 @@ from pathlib import Path
 
 import numpy as np
 
+T_START = time.perf_counter()
 ROOT = Path(__file__).resolve().parent
 sys.path[:0] = [str(ROOT / "recommendation-system_amd"), str(ROOT), str(ROOT / "tests" / "golden")]
 
@@ -66,14 +71,25 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def stamp(what: str):
+    """Seconds since the process started, on stderr: where a run's time outside its steps goes."""
+    log(f"[{time.perf_counter() - T_START:7.2f} s] {what}")
+
+
 def make_data(w: dict, rank: int, world: int):
+    from concurrent.futures import ThreadPoolExecutor
+
     from gen import synth_csr, synth_embeddings
-    E = synth_embeddings(w["items"], w["d"], seed=1)
-    if w.get("shard_gen"):  # this rank's users only (a 1/8 shard: the 8-GPU split), from a per-rank seed
-        X = synth_csr(w["users"] // 8, w["items"], lam=w["lam"], seed=1000 + rank)
-        return X, E, np.arange(X.shape[0])
-    X = synth_csr(w["users"], w["items"], lam=w["lam"], seed=0)
-    return X, E, np.arange(X.shape[0])  # every rank holds every user and takes its slice of each global batch
+    # E and X come from generators of their own (numpy draws with the GIL released), so the two are drawn side
+    # by side: same values, and the set-up of a Syn-10M run is shorter by the time of the CSR
+    with ThreadPoolExecutor(max_workers=1) as pool:
+        if w.get("shard_gen"):  # this rank's users only (a 1/8 shard: the 8-GPU split), from a per-rank seed
+            fx = pool.submit(synth_csr, w["users"] // 8, w["items"], lam=w["lam"], seed=1000 + rank)
+        else:
+            fx = pool.submit(synth_csr, w["users"], w["items"], lam=w["lam"], seed=0)
+        E = synth_embeddings(w["items"], w["d"], seed=1)
+        X = fx.result()
+    return X, E, np.arange(X.shape[0])  # (unsharded: every rank holds every user and takes its slice of each batch)
 
 
 def batch_stats(X, users, B: int, gen_seed: int = 0, samples: int = 32) -> tuple[float, float]:
@@ -250,6 +266,49 @@ def roofline_models(w: dict, precision: str, B: int, fused, X, users, rank: int,
     return out
 
 
+DUMP_W1_ITEMS = 4096  # W1 columns written by --dump-outputs: this many of the most popular items + as many drawn
+
+
+def dump_outputs(path: str, epoch_losses: dict, fused, model, B: int) -> None:
+    """What the timed path leaves its caller after the last timed step, as <path>/<name>.npy (float32 / float64).
+
+    epoch_loss: run_epoch's return of the last timed call (mean total / recon / KL loss of its steps, float64).
+    step_loss, step_heads: the last step's loss3 and its encoder heads (mu | logvar of its B users).
+    param.<name>: every trained parameter after the last step (the module's parameters are views of the fused
+      trainer's flat buffer). encoder.0.weight (hidden x items, 2 GB at the north-star shape) is written as a
+      fixed sample of its item columns: the first DUMP_W1_ITEMS items (the Zipf head, rows every batch updates)
+      and DUMP_W1_ITEMS more drawn with a fixed seed; w1_items holds their ids. About 25 MB in all by default.
+    """
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {"epoch_loss": np.array([epoch_losses[k] for k in ("total_loss", "recon_loss", "kl_loss")],
+                                     dtype=np.float64)}
+    bf = fused._bufs[(B, True)]
+    arrays["step_loss"] = bf.loss3.detach().float().cpu().numpy()
+    arrays["step_heads"] = bf.heads.detach().float().cpu().numpy()
+    n_items = fused.layout.n_items
+    items = np.arange(n_items)
+    if n_items > 2 * DUMP_W1_ITEMS:
+        rest = np.random.default_rng(20240607).choice(n_items - DUMP_W1_ITEMS, size=DUMP_W1_ITEMS, replace=False)
+        items = np.concatenate([np.arange(DUMP_W1_ITEMS), DUMP_W1_ITEMS + np.sort(rest)])
+    arrays["w1_items"] = items.astype(np.float64)
+    idx = torch.as_tensor(items, device=fused.device)
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        t = p.detach()
+        if name == "encoder.0.weight":
+            t = t.index_select(1, idx)
+        arrays["param." + name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the 64 MB bound")
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+    log(f"dump-outputs: {len(arrays)} arrays, {total / 1e6:.1f} MB -> {out}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -258,10 +317,16 @@ def main():
     ap.add_argument("--workload", default="syn10m", choices=sorted(WORKLOADS))
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp8", "fp32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the per-kernel probe passes (roofline, launch_us) and the "
+                         "CPU baseline; a plain run reports the headline figures only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (losses, parameters) as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=60.0,
-                    help="CPU baseline: time >= 20 steps or this many seconds, whichever comes first (SURVEY §8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--probe-steps", type=int, default=50)
+                    help="--full, CPU baseline: time >= 20 steps or this many seconds, whichever comes first "
+                         "(SURVEY §8d)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--probe-steps", type=int, default=50, help="--full: eager steps per probed kernel family")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: --batch-size users per GPU per step (default); strong: --global-batch users per "
                          "step split over the GPUs (SURVEY §8d: both curves)")
@@ -298,12 +363,15 @@ def main():
     from hvae.executor import ConstBeta, FusedTrainer
     from src.ml.model import HybridVAE
 
+    stamp("imports done")
     X, E, users = make_data(w, rank, world)
+    stamp("synthetic data generated")
     torch.manual_seed(0)
     model = HybridVAE(w["items"], E, latent_dim=w["latent"], hidden_dims=w["hidden"], dropout=w["dropout"],
                       beta=w["beta"]).to(device)
     fused = FusedTrainer(model, device, lr=w["lr"], precision=args.precision, seed=1234, use_graphs=True,
                          process_group=group)
+    stamp("model and fused trainer on the device")
     data = fused.device_data(X, users)
     data.dp_global = world > 1 and not w.get("shard_gen")  # per-rank generated shards are already disjoint
     B = w["batch"]
@@ -312,13 +380,17 @@ def main():
     gen = torch.Generator(device=device).manual_seed(rank)  # epoch orders drawn on the GPU
 
     def run(nsteps):
-        done = 0
+        done, losses = 0, None
         while done < nsteps:
             k = min(nsteps - done, n_per_epoch)
-            fused.run_epoch(data, B, True, beta, w["dropout"], generator=gen, max_batches=k)
+            losses = fused.run_epoch(data, B, True, beta, w["dropout"], generator=gen, max_batches=k)
             done += k
+        return losses  # of the last call: the mean losses of its k steps
 
+    stamp("interactions on the device")
     run(args.warmup)
+    torch.cuda.synchronize()
+    stamp(f"{args.warmup} warm-up steps done")
     # the wall time is never taken from probed steps: an armed probe puts a 200-us hold kernel in front of every
     # bracketed launch (csrc/hvae_abi.hip, probe_mark), so the library is disarmed here and armed only after the
     # timed region, for the separate probe pass below
@@ -328,7 +400,7 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run(args.steps)
+    last_losses = run(args.steps)
     torch.cuda.synchronize()
     if group is not None:
         torch.distributed.barrier()
@@ -339,59 +411,66 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     ms = elapsed / args.steps * 1e3
+    stamp(f"{args.steps} timed steps done")
     value = world * B * args.steps / elapsed
 
-    # ---- live per-kernel timing: libhvae brackets each launch of the armed kernel family with a hipEvent pair
-    # recorded on the stream it runs on (eager steps of the same workload, after the timed region)
-    import ctypes as C
-    from hvae._lib import check, lib
+    if args.dump_outputs and rank == 0:  # before the probe passes of --full train on
+        dump_outputs(args.dump_outputs, last_losses, fused, model, B)
+
     from hvae.provenance import kernel_source_digest
-    N, H, D, Lt = w["items"], w["hidden"][0], w["d"], w["latent"]
-    fused.use_graphs = False
+    D = w["d"]
+    roofline = kernels_out = launch_us = cpu = None
+    if args.full:
+        # ---- live per-kernel timing: libhvae brackets each launch of the armed kernel family with a hipEvent pair
+        # recorded on the stream it runs on (eager steps of the same workload, after the timed region)
+        import ctypes as C
+        from hvae._lib import check, lib
+        fused.use_graphs = False
 
-    def probe(name):
-        check(lib().hvae_probe_arm(name.encode(), 64 * args.probe_steps), "probe_arm")
-        run(args.probe_steps)
-        torch.cuda.synchronize()
-        avg, n = C.c_double(), C.c_int()
-        check(lib().hvae_probe_collect(C.byref(avg), C.byref(n)), "probe_collect")
-        check(lib().hvae_probe_arm(None, 0), "probe_disarm")
-        return avg.value * 1e-6, n.value // args.probe_steps
+        def probe(name):
+            check(lib().hvae_probe_arm(name.encode(), 64 * args.probe_steps), "probe_arm")
+            run(args.probe_steps)
+            torch.cuda.synchronize()
+            avg, n = C.c_double(), C.c_int()
+            check(lib().hvae_probe_collect(C.byref(avg), C.byref(n)), "probe_collect")
+            check(lib().hvae_probe_arm(None, 0), "probe_disarm")
+            return avg.value * 1e-6, n.value // args.probe_steps
 
-    kernels = {name: probe(name) for name in FAMILIES}
-    fused.use_graphs = True
-    roof = roofline_models(w, args.precision, B, fused, X, users, rank, kernels)
-    # the dominant kernel family: the largest per-step total (average launch x launches per step) among the
-    # families with an algorithmic model (the row-parallel MLP launches against the L2-served rate their weight
-    # streams are read at)
-    dom = max((k for k in roof if roof[k]["peak"]), key=lambda k: kernels[k][0] * max(kernels[k][1], 1))
-    r = roof[dom]
-    traffic, stale = None, None
-    pmc = ROOT / "profiles" / (f"pmc_{args.workload}.json" if args.precision == "bf16"
-                               else f"pmc_{args.workload}_{args.precision}.json")
-    if pmc.exists():
-        try:
-            doc = json.loads(pmc.read_text())
-            if doc.get("src_sha") == kernel_source_digest():
-                traffic = doc.get(dom, {}).get("hbm_bytes_per_launch")
-            else:  # measured on other kernel sources: refuse it
-                stale = {"pmc_src_sha": doc.get("src_sha"), "tree_src_sha": kernel_source_digest()}
-        except (ValueError, OSError):
-            traffic = None
-    roofline = {"bound": r["bound"], "achieved": round(r["achieved"], 2), "peak": r["peak"], "unit": r["unit"],
-                "frac": round(r["achieved"] / r["peak"], 4), "traffic": traffic, "kernel": dom,
-                "avg_launch_us": round(r["avg_launch_us"], 2),
-                "alg_per_launch": r["alg_per_launch"]}
-    if r.get("l2_lds"):  # the sweep's second bound: L2 -> LDS bytes of its user blocks
-        roofline["l2_lds"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r["l2_lds"].items()}
-    if stale:
-        roofline["traffic_stale"] = stale
-    launch_us = {k: {"avg_us": round(v[0] * 1e6, 2), "launches_per_step": v[1],
-                     "us_per_step": round(v[0] * 1e6 * v[1], 2)} for k, v in kernels.items()}
+        kernels = {name: probe(name) for name in FAMILIES}
+        fused.use_graphs = True
+        roof = roofline_models(w, args.precision, B, fused, X, users, rank, kernels)
+        # the dominant kernel family: the largest per-step total (average launch x launches per step) among the
+        # families with an algorithmic model (the row-parallel MLP launches against the L2-served rate their weight
+        # streams are read at)
+        dom = max((k for k in roof if roof[k]["peak"]), key=lambda k: kernels[k][0] * max(kernels[k][1], 1))
+        r = roof[dom]
+        traffic, stale = None, None
+        pmc = ROOT / "profiles" / (f"pmc_{args.workload}.json" if args.precision == "bf16"
+                                   else f"pmc_{args.workload}_{args.precision}.json")
+        if pmc.exists():
+            try:
+                doc = json.loads(pmc.read_text())
+                if doc.get("src_sha") == kernel_source_digest():
+                    traffic = doc.get(dom, {}).get("hbm_bytes_per_launch")
+                else:  # measured on other kernel sources: refuse it
+                    stale = {"pmc_src_sha": doc.get("src_sha"), "tree_src_sha": kernel_source_digest()}
+            except (ValueError, OSError):
+                traffic = None
+        roofline = {"bound": r["bound"], "achieved": round(r["achieved"], 2), "peak": r["peak"], "unit": r["unit"],
+                    "frac": round(r["achieved"] / r["peak"], 4), "traffic": traffic, "kernel": dom,
+                    "avg_launch_us": round(r["avg_launch_us"], 2),
+                    "alg_per_launch": r["alg_per_launch"]}
+        if r.get("l2_lds"):  # the sweep's second bound: L2 -> LDS bytes of its user blocks
+            roofline["l2_lds"] = {k: (round(v, 4) if isinstance(v, float) else v) for k, v in r["l2_lds"].items()}
+        if stale:
+            roofline["traffic_stale"] = stale
+        launch_us = {k: {"avg_us": round(v[0] * 1e6, 2), "launches_per_step": v[1],
+                         "us_per_step": round(v[0] * 1e6 * v[1], 2)} for k, v in kernels.items()}
+        kernels_out = {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()}
+                       for k, v in roof.items()}
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(w, X, E, args.cpu_seconds)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(w, X, E, args.cpu_seconds)
 
     if rank == 0:
         out = {
@@ -401,6 +480,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms, 4),
             "higher_is_better": True,
             "scaling": args.scaling,
@@ -412,8 +492,7 @@ def main():
                        "latent": w["latent"], "hidden": w["hidden"], "global_batch": B * world,
                        "batch_per_gpu": B, "parallelism": f"dp{world}", "decoder": args.precision},
             "roofline": roofline,
-            "kernels": {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()}
-                        for k, v in roof.items()},
+            "kernels": kernels_out,
             "src_sha": kernel_source_digest(),
             "launch_us": launch_us,
             "cpu_baseline": cpu,
