@@ -501,7 +501,11 @@ int hvae_adam_lazy_catchup_csr(const hvae_adam* cfg, const float* tab, float* p,
  *     the recorded step, i.e. no clip in between);
  *   hvae_adam_lazy_pending -- every pending row no catch-up has claimed, and the recorded step's sweep range
  *     (hvae_adam_lazy_sweep_period), on any stream, beside the next step's forward; max_rows bounds the rows
- *     recorded (grid size). A second run is a no-op.
+ *     recorded (grid size). A second run is a no-op. Precondition: the record is applied only while
+ *     *cfg->step_dev (required, non-NULL) still equals the recorded step, as for the catch-up; with any other
+ *     step count -- nothing recorded yet, or step_dev set back or forward since (a loaded optimizer state) --
+ *     the record is stale and the call changes nothing. A caller that rewrites step_dev and last_step itself
+ *     should also zero pend->hdr, so that a record cannot come back to life when step_dev returns to its step.
  * The recorded gradient rows (rg->rows) must stay as they are until hvae_adam_lazy_pending has run, and it must
  * run before the next hvae_adam_lazy / _defer, a catch-up over all rows, or any other read of W1t, m or v.
  *   pend->slot_of [N] int32, pend->item_of [N] int32, pend->hdr 32 bytes of device memory, zeroed once. */

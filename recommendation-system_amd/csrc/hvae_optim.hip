@@ -547,6 +547,12 @@ __global__ void __launch_bounds__(256) k_adam_lazy(AdamArgs a, float2* __restric
 // blocks [nb_rows, nb_rows + nb_sweep) take step t's sweep range (k_adam_lazy's sweep: rows without a pending
 // update brought through step t; a row the catch-up moved p of to t replays m and v alone). Same float operations
 // as the undeferred update, so the rows are bitwise k_adam_lazy's. A second run finds nothing left to do.
+// The record is live only while *step_dev is still the recorded step (k_adam_catchup_csr's pend_on): once the
+// counter has moved on -- or back, a reloaded optimizer state -- the record is stale, its sweep range would be
+// replayed through the old step from old tab[] entries and stamped with it, and nothing runs. What this cannot
+// see: a caller that sets step_dev back and later reaches the record's step again without a new record in between
+// finds it live once more -- whoever rewrites step_dev and last_step zeroes the header (include/hvae.h;
+// FusedTrainer.mark_all_current does).
 __global__ void __launch_bounds__(256) k_adam_pending(AdamArgs a, const float2* __restrict__ tab,
                                                      float* __restrict__ p, float* __restrict__ m,
                                                      float* __restrict__ v, int32_t* __restrict__ last_step,
@@ -555,7 +561,7 @@ __global__ void __launch_bounds__(256) k_adam_pending(AdamArgs a, const float2* 
                                                      const PendHdr* __restrict__ hdr, int64_t N, int64_t H,
                                                      int nb_rows, int nb_sweep, int period, RowMap rm) {
   const int64_t t64 = hdr->t;
-  if (t64 <= 0) return;
+  if (t64 <= 0 || t64 != load_step(a.step_dev)) return;
   const int t = (int)t64;
   const float* __restrict__ rows = hdr->rows;
   const int64_t ld = hdr->ld;
@@ -793,8 +799,8 @@ extern "C" int hvae_adam_lazy_catchup_csr_pending(const hvae_adam* cfg, const fl
 extern "C" int hvae_adam_lazy_pending(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v,
                                       int32_t* last_step, int64_t N, int64_t H, int64_t max_rows,
                                       const hvae_adam_pend* pend, void* stream) {
-  HVAE_REQUIRE(cfg && tab && p && m && v && last_step && pend && pend->slot_of && pend->item_of && pend->hdr &&
-                   H % 4 == 0 && N >= 0 && max_rows >= 0,
+  HVAE_REQUIRE(cfg && cfg->step_dev && tab && p && m && v && last_step, "hvae_adam_lazy_pending: bad args");
+  HVAE_REQUIRE(pend && pend->slot_of && pend->item_of && pend->hdr && H % 4 == 0 && N >= 0 && max_rows >= 0,
                "hvae_adam_lazy_pending: bad args");
   HVAE_REQUIRE(((uintptr_t)p % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
                "hvae_adam_lazy_pending: 16-B alignment required");

@@ -988,6 +988,10 @@ class FusedTrainer:
     def mark_all_current(self):
         """Every row has had every step applied (after an external dense update of W1t)."""
         self._resolve_pending()
+        if self.adam_defer:
+            # step_dev may have moved (a loaded optimizer state): the resolved record must not look live to a later
+            # hvae_adam_lazy_pending that runs before the next hvae_adam_lazy_defer writes a new one
+            self.pend_hdr.zero_()
         self.last_step.copy_(self.step_dev.to(torch.int32).expand_as(self.last_step))
 
     def _check_steps(self, more: int):

@@ -242,6 +242,52 @@ def test_deferred_adam_is_bitwise(hip_device, wd, at, graphs, monkeypatch):
     assert torch.equal(fa, fb) and torch.equal(ma, mb) and torch.equal(sa, sb)
 
 
+@pytest.mark.parametrize("graphs", [True, False])
+@pytest.mark.parametrize("wd,at", [(0.0, "fwd"), (0.01, "sweep")])
+def test_deferred_adam_survives_state_reload(hip_device, wd, at, graphs, monkeypatch):
+    """A checkpoint reload moves step_dev backwards (HipAdam.load_state_dict) while the header of the last deferred
+    step is still in device memory: two epochs, then the model and optimizer state taken after the first are loaded
+    again and a third epoch runs. The deferred update must stay bitwise the undeferred one. A stale record replayed by
+    the next deferring step's hvae_adam_lazy_pending (it ran whenever a step had ever been recorded) pushes the old
+    step's sweep range through the old step and stamps it with a step in the future."""
+    import copy
+    monkeypatch.setenv("HVAE_PLAN_SIDE_MIN_BATCH", "32")  # B = 32 defers, the tail of 2 does not
+    monkeypatch.setenv("HVAE_ENC_LAZY_READ", "0")
+    monkeypatch.setenv("HVAE_DEFER_AT", at)
+    from hvae.executor import ConstBeta, FusedTrainer
+    from src.ml.model import HybridVAE
+    from src.ml.train import HipAdam
+    X = synth_csr(290, 700, seed=13)
+    E = synth_embeddings(700, 128, seed=14)
+    outs = []
+    for defer in ("0", "1"):
+        monkeypatch.setenv("HVAE_ADAM_DEFER", defer)
+        torch.manual_seed(0)
+        model = HybridVAE(700, E, latent_dim=64, hidden_dims=[128], dropout=0.3, beta=0.2).to(hip_device)
+        fused = FusedTrainer(model, hip_device, weight_decay=wd, precision="bf16", seed=77, use_graphs=graphs)
+        opt = HipAdam(model.parameters(), fused, lr=fused.lr, weight_decay=wd)
+        assert fused._defers(32) == (defer == "1") and not fused._defers(2)
+        data = fused.device_data(X, list(range(290)))
+        gen = torch.Generator().manual_seed(6)
+        r = [fused.run_epoch(data, 32, True, ConstBeta(0.2), 0.3, generator=gen)]
+        model_sd = {k: v.detach().clone() for k, v in model.state_dict().items()}
+        opt_sd = copy.deepcopy(opt.state_dict())
+        r.append(fused.run_epoch(data, 32, True, ConstBeta(0.2), 0.3, generator=gen))
+        assert int(fused.step_dev.item()) == 20
+        model.load_state_dict(model_sd)
+        opt.load_state_dict(opt_sd)
+        assert int(fused.step_dev.item()) == 10
+        r.append(fused.run_epoch(data, 32, True, ConstBeta(0.2), 0.3, generator=gen))
+        fused.flush()
+        outs.append((r, fused.flat.clone(), fused.m.clone(), fused.v.clone(), fused.step_dev.clone()))
+    (ra, fa, ma, sa, na), (rb, fb, mb, sb, nb) = outs
+    assert torch.equal(na, nb) and int(na.item()) == 20
+    for name, a, b in (("flat", fa, fb), ("m", ma, mb), ("v", sa, sb)):
+        assert torch.equal(a, b), f"{name}: deferred differs from undeferred after the reload, " \
+                                  f"max |d| {float((a - b).abs().max()):.3e} in {int((a != b).sum())} elements"
+    assert ra == rb
+
+
 def test_annealed_epoch_graph_is_bitwise_eager(hip_device):
     """AnnealedVAE (reference src/ml/model.py:295-334, stepped once per train batch, src/ml/train.py:74-76): the
     schedule evaluated on the device inside the captured step (AnnealedBeta -> hvae_anneal_beta) replays one graph
