@@ -362,7 +362,7 @@ int hvae_gemm_f32_multi(const hvae_gemm_desc* d, int n, void* stream);
  *   HVAE_FP8:  the bf16 E [N, D] as above (score bound, exact fixups), then at a
  *              256-B aligned offset ceil(N/64) tiles of [64][D] e4m3 (16-B chunks
  *              XOR-swizzled by item row; tail items 0), then the int exponent ke
- *              of E's scale (E8 = E 2^ke); D in {128, 256, 384, 768};
+ *              of E's scale (E8 = E 2^ke); D in {128, 256, 384, 512, 768};
  *   HVAE_F32:  E itself [N, D].
  * Every `E` argument of the decoder functions below is this image. */
 size_t hvae_decoder_image_bytes(int dtype, int64_t N, int64_t D);
@@ -375,7 +375,10 @@ size_t hvae_decoder_workspace(int dtype, int64_t nb, int64_t N, int64_t D);
  * user block streams all of E from L2 into LDS once, so a sweep moves ceil(nb / this) x the image bytes
  * (the L2 -> LDS bound the bench reports beside the MFMA one). Informational; 0 for bad arguments. */
 int64_t hvae_decoder_users_per_tile(int dtype, int64_t nb, int64_t N, int64_t D);
-/* 1 if this build has a streaming decoder kernel for (dtype, D). */
+/* 1 if this build has a streaming decoder kernel for (dtype, D): HVAE_BF16 at D in {64, 128, 256, 384, 512, 768,
+ * 1024}, HVAE_F32 at {32, 64, 128, 256, 384, 512}, HVAE_FP8 at {128, 256, 384, 512, 768}. fp32 at 768 / 1024 and
+ * fp8 at 1024 are refused (HVAE_ERR_UNSUPPORTED from the decoder calls): registers and LDS, DESIGN.md section 7.
+ * A bf16 / fp8 image is addressed in 32 bits, so N D < 2^30 (N < 2^20 items at D = 1024). */
 int hvae_decoder_supported(int dtype, int64_t D);
 /* *out = max_i ||E_i||_2 of an fp32 / bf16 [N, D] matrix (computed once: E is frozen). */
 int hvae_row_norm_max(int dtype, const void* E, int64_t N, int64_t D, float* out, void* stream);

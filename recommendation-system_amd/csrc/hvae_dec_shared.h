@@ -99,12 +99,13 @@ constexpr float kMinL = 8.75651e-27f;
 
 template <int D, int DS>
 constexpr int d2_tile_bytes() { return ((D + 127) / 128) * 8192; }
-// DS = 2 exchange buffers: double-buffered by tile parity, or single (one more barrier per tile) where the
-// tile is large (d = 768) so that the ring keeps three stages
+// D-split (DS = 2, 4) exchange buffers: double-buffered by tile parity, or single (one more barrier per tile)
+// where the tile is large (d > 384) so that the ring keeps as many stages as fit (three at 512 and 768, two at
+// 1024: 2 x 64 KiB + 16 KiB)
 template <int D>
 constexpr int d2_xbufs() { return D > 384 ? 1 : 2; }
 template <int D, int DS, int NW>
-constexpr int d2_xbytes() { return DS == 2 ? d2_xbufs<D>() * NW * 4096 : 0; }
+constexpr int d2_xbytes() { return DS >= 2 ? d2_xbufs<D>() * NW * 4096 : 0; }
 template <int D, int DS, int NW>
 constexpr int d2_stages() {
   return (160 * 1024 - d2_xbytes<D, DS, NW>()) / d2_tile_bytes<D, DS>() >= 6
@@ -192,8 +193,8 @@ struct DecPlan {
   int v5;    // bf16 version-5 sweep (k_dec5_bf16, D = 768: 8 waves, GEMM1 and GEMM2 on different waves)
   int v6;    // bf16 version-6 sweep (k_dec6_bf16, D = 768: 96 users per E tile, task plan p6)
   Dec6Plan p6;
-  int ds;    // its D split (1 or 2)
-  int nw;    // its waves per block (4, or 8 with ds = 2)
+  int ds;    // its D split (1, 2, or 4 at D = 1024)
+  int nw;    // its waves per block (4, or 8 with ds = 2 at D <= 384)
   int64_t upb;
 };
 

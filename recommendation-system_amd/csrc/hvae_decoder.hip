@@ -56,8 +56,12 @@ namespace hvae {
 // DS = 2: waves (ug, dh) = (w & 1, w >> 1): 2 user groups x 2 halves of D, each
 // wave's GEMM1 sums over its half and the two halves' partial S^T tiles are added
 // through LDS (double-buffered by tile parity); both waves of a user group run the
-// softmax, each accumulates O for its half of D. Serves D = 768 (U 96 + O 192 per
-// wave) and small batches (64 users per block keeps all 4 waves busy).
+// softmax, each accumulates O for its half of D. Serves D = 512 (U 64 + O 128 per wave), D = 768 in the A/B
+// library (U 96 + O 192) and small batches (64 users per block keeps all 4 waves busy).
+// DS = 4 (D = 1024): the block's 4 waves are the 4 quarters of D of ONE group of 32 users (U 64 + O 128 per
+// wave; in halves O alone would take 256 registers). All four partial S^T tiles cross the exchange buffer and
+// every wave adds the four in quarter order, so the group holds bitwise one S^T, one offset and one l. A tile is
+// 64 KiB: two ring slots (NS = 2: the next tile's LDS-DMA is issued after the barrier that frees its slot).
 
 template <int D, int DS, int NW, bool WITH_O>
 __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__ U, int64_t ldu,
@@ -74,8 +78,10 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
   constexpr int NS = d2_stages<D, DS, NW>();
   constexpr int UPB = 32 * NW / DS;
   constexpr int HALF = NW / 2;          // DS = 2: partner wave = w ^ HALF
+  constexpr int NUG = NW / DS;          // user groups per block; the DS waves of group ug are ug + NUG k
   constexpr bool kSpread = DS == 2 && NS >= 3;  // LDS-DMA pieces issued between GEMM1's MFMA pairs
-  static_assert(NW == 4 || (NW == 8 && DS == 2), "8-wave blocks split D");
+  static_assert(DS == 1 || DS == 2 || DS == 4, "D is whole, halved or quartered");
+  static_assert(NW == 4 || (NW == 8 && DS == 2), "8-wave blocks split D in halves");
   static_assert(DW % 32 == 0 && KS % 2 == 0, "D / DS must be a multiple of 32");
   static_assert(NS >= 2, "LDS ring too small");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -84,7 +90,7 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
 
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, col = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int ug = DS == 1 ? w : (w % HALF), dh = DS == 1 ? 0 : (w / HALF);
+  const int ug = DS == 1 ? w : (w % NUG), dh = DS == 1 ? 0 : (w / NUG);
   const int split = blockIdx.x % splits;
   const int64_t ub = blockIdx.x / splits;
   const int64_t u0 = ub * UPB + ug * 32;
@@ -117,6 +123,17 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
       if (user < nb) {
         const float4 a = *reinterpret_cast<const float4*>(U + user * ldu + obase + 16 * ks + 8 * h);
         const float4 b = *reinterpret_cast<const float4*>(U + user * ldu + obase + 16 * ks + 8 * h + 4);
+        usq += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w) + (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
+      }
+    }
+  }
+  if constexpr (DS == 4) {  // |u| over the whole row, summed in column order: one bound (and offset m) per group
+    usq = 0.f;
+#pragma unroll 1
+    for (int c = 0; c < D / 16; ++c) {
+      if (user < nb) {
+        const float4 a = *reinterpret_cast<const float4*>(U + user * ldu + 16 * c + 8 * h);
+        const float4 b = *reinterpret_cast<const float4*>(U + user * ldu + 16 * c + 8 * h + 4);
         usq += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w) + (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
       }
     }
@@ -198,7 +215,7 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
     }
     return s;
   };
-  // DS = 2: this wave's partial S^T of a tile <-> its partner's, [r4][lane] float4 rows
+  // DS >= 2: this wave's partial S^T of a tile <-> those of its group's other waves, [r4][lane] float4 rows
   auto xput = [&](int par, const f32x16& s) {
     float* xb = xbuf + (((par % XB) * NW + w) * 4) * 256;
 #pragma unroll
@@ -207,11 +224,29 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
                                                                          s[4 * r4 + 3]);
   };
   auto xadd = [&](int par, f32x16& s) {
-    const float* xb = xbuf + (((par % XB) * NW + (w ^ HALF)) * 4) * 256;
+    if constexpr (DS == 2) {
+      const float* xb = xbuf + (((par % XB) * NW + (w ^ HALF)) * 4) * 256;
 #pragma unroll
-    for (int r4 = 0; r4 < 4; ++r4) {
-      const float4 v = *reinterpret_cast<const float4*>(xb + r4 * 256 + lane * 4);
-      s[4 * r4] += v.x; s[4 * r4 + 1] += v.y; s[4 * r4 + 2] += v.z; s[4 * r4 + 3] += v.w;
+      for (int r4 = 0; r4 < 4; ++r4) {
+        const float4 v = *reinterpret_cast<const float4*>(xb + r4 * 256 + lane * 4);
+        s[4 * r4] += v.x; s[4 * r4 + 1] += v.y; s[4 * r4 + 2] += v.z; s[4 * r4 + 3] += v.w;
+      }
+    } else {
+      // DS = 4: all four quarters' partials (this wave's own included) from the buffer in quarter order, so
+      // that the four waves of a group hold bitwise the same S^T (one softmax, one l per user)
+#pragma unroll
+      for (int k = 0; k < DS; ++k) {
+        const float* xb = xbuf + (((par % XB) * NW + ug + NUG * k) * 4) * 256;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const float4 v = *reinterpret_cast<const float4*>(xb + r4 * 256 + lane * 4);
+          if (k == 0) {
+            s[4 * r4] = v.x; s[4 * r4 + 1] = v.y; s[4 * r4 + 2] = v.z; s[4 * r4 + 3] = v.w;
+          } else {
+            s[4 * r4] += v.x; s[4 * r4 + 1] += v.y; s[4 * r4 + 2] += v.z; s[4 * r4 + 3] += v.w;
+          }
+        }
+      }
     }
   };
 
@@ -275,7 +310,7 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
   float bound = 0.f;
   if (t_beg < t_end && wave_active) {
     s_cur = gemm1(lds, [](int) {});
-    if (DS == 2 && DEC2_ABL != 4) xput((int)(t_beg & 1), s_cur);
+    if (DS >= 2 && DEC2_ABL != 4) xput((int)(t_beg & 1), s_cur);
   }
   bound = sqrtf(usq) * emax * 1.02f;
 
@@ -296,14 +331,14 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
     const int64_t t_dma = min(t + NS - 1, t_end - 1);
     const int s_dma = cur == 0 ? NS - 1 : cur - 1;
     if (DEC2_ABL != 1 && NS >= 3 && (!kSpread || !wave_active)) issue(t_dma, s_dma);  // idle waves load too
-    if constexpr (DS == 2 && XB == 1 && DEC2_ABL != 4) {  // single exchange buffer: everyone has read S(t) before S(t+1) lands
+    if constexpr (DS >= 2 && XB == 1 && DEC2_ABL != 4) {  // single exchange buffer: everyone has read S(t) before S(t+1) lands
       if (wave_active) xadd((int)(t & 1), s_cur);
       lds_fence();
       __builtin_amdgcn_s_barrier();
       lds_fence();
     }
     if (wave_active) {
-      if (DS == 2 && XB == 2 && DEC2_ABL != 4) xadd((int)(t & 1), s_cur);
+      if (DS >= 2 && XB == 2 && DEC2_ABL != 4) xadd((int)(t & 1), s_cur);
       if (t == ntiles - 1 && (N % kBfTI) != 0) {  // rows past N (read as 0) leave the softmax
         const int lim = (int)(N - t * kBfTI) - 4 * h;  // rows of this lane's half at or past it are tail
 #pragma unroll
@@ -343,7 +378,7 @@ __global__ void __launch_bounds__(64 * NW) k_dec2_bf16(const float* __restrict__
         if (DEC2_ABL != 1 && kSpread && PW * g / NG < PW * (g + 1) / NG)
           issue_range(t_dma, s_dma, PW * g / NG, PW * (g + 1) / NG);
       });
-      if (DS == 2 && more && DEC2_ABL != 4) xput((int)((t + 1) & 1), s_nx);
+      if (DS >= 2 && more && DEC2_ABL != 4) xput((int)((t + 1) & 1), s_nx);
       bf16x8 pf[2];
       pf[0] = __builtin_bit_cast(bf16x8, make_uint4(pk[0], pk[1], pk[2], pk[3]));
       pf[1] = __builtin_bit_cast(bf16x8, make_uint4(pk[4], pk[5], pk[6], pk[7]));
@@ -430,7 +465,7 @@ __global__ void __launch_bounds__(256) k_dec_fp8(const float* __restrict__ U, in
   constexpr int PW = TB / 4096;          // 1-KiB LDS-DMA pieces per wave per tile
   constexpr int NS = f8_stages<D>();
   constexpr int UPB = 128 / DS;          // users per block
-  static_assert(D % 64 == 0 && (DS == 1 ? (D <= 384 && NS >= 3) : (D == 768 && NS == (F8_DS2_RING ? 3 : 2))),
+  static_assert(D % 64 == 0 && (DS == 1 ? (D <= 384 && NS >= 3) : ((D == 512 || D == 768) && NS == (F8_DS2_RING ? 3 : 2))),
                 "fp8 decoder shape");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
 
@@ -1520,8 +1555,8 @@ __global__ void __launch_bounds__(256) k_row_norm_max(int dtype, const void* __r
 
 
 // A/B switches (environment, read at plan time) exist only in variant builds (-DHVAE_AB=1, scripts/build_ab.sh);
-// the product library runs one sweep per (dtype, D): bf16 version 2 at D <= 384, version 5 at D = 768, the fp8
-// ring, the fp32 sweep.
+// the product library runs one sweep per (dtype, D): bf16 version 2 at D <= 384, 512 and 1024, version 5 at
+// D = 768, the fp8 ring, the fp32 sweep.
 #if HVAE_AB
 static int env_int(const char* name, int dflt) {
   const char* v = getenv(name);
@@ -1552,7 +1587,9 @@ static int dec_forced_nw() { return 0; }
 static int env_int(const char*, int dflt) { return dflt; }
 #endif
 
-static bool v2_supported(int64_t D) { return D == 64 || D == 128 || D == 256 || D == 384 || D == 768; }
+static bool v2_supported(int64_t D) {
+  return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
+}
 // HVAE_DEC_V3=0 keeps the version-2 sweep at D = 768 (A/B; read at every plan, so a test can switch it)
 static bool v3_supported(int64_t D) { return D == 768 && env_int("HVAE_DEC_V3", 1) != 0; }
 // HVAE_DEC_V4=0 keeps version 3 at D = 768 (A/B; read at every plan)
@@ -1609,7 +1646,7 @@ static DecPlan dec_plan(int dtype, int64_t nb, int64_t N, int64_t D) {
 #else
   p.v6 = 0;
 #endif
-  p.ds = p.v2 && (D > 384 || nb <= 64) ? 2 : 1;
+  p.ds = p.v2 && D == 1024 ? 4 : p.v2 && (D > 384 || nb <= 64) ? 2 : 1;  // 1024: quarters, 32 users per block
   if (p.v2 && D <= 384 && (dec_forced_ds() == 1 || dec_forced_ds() == 2)) p.ds = dec_forced_ds();
   p.nw = p.v2 && p.ds == 2 && nb > 64 && D <= 384 ? 8 : 4;
   if (p.v2 && p.ds == 2 && D <= 384 && (dec_forced_nw() == 4 || dec_forced_nw() == 8)) p.nw = dec_forced_nw();
@@ -1663,7 +1700,8 @@ static int launch_bf16_v2_nw(const float* U, int64_t ldu, const void* E, const f
 template <int D, int DS, bool WO>
 static int launch_bf16_v2(const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
                           const DecPlan& p, DecOut o, hipStream_t st) {
-  if constexpr (DS == 2 && d2_stages<D, 2, 8>() >= 3) {
+  // 8 waves (two per SIMD) only where each fits 256 registers: at D = 512 that form spills
+  if constexpr (DS == 2 && D <= 384 && d2_stages<D, 2, 8>() >= 3) {
     if (p.nw == 8) return launch_bf16_v2_nw<D, 2, 8, WO>(U, ldu, E, enorm, nb, N, p, o, st);
   }
   return launch_bf16_v2_nw<D, DS, 4, WO>(U, ldu, E, enorm, nb, N, p, o, st);
@@ -1713,6 +1751,7 @@ static int dispatch(int dtype, const float* U, int64_t ldu, const void* E, const
       case 128: return launch_fp8<128, WO>(U, ldu, E, enorm, nb, N, p, o, st);
       case 256: return launch_fp8<256, WO>(U, ldu, E, enorm, nb, N, p, o, st);
       case 384: return launch_fp8<384, WO>(U, ldu, E, enorm, nb, N, p, o, st);
+      case 512: return launch_fp8<512, WO>(U, ldu, E, enorm, nb, N, p, o, st);
       case 768:
 #if HVAE_AB  // HVAE_DEC_F8V4=1 runs the version-4 structure, HVAE_DEC_F8V5=0 the D-split ring
         if (env_int("HVAE_DEC_F8V4", 0) != 0) return ab_dec_f8v4(WO, U, ldu, E, enorm, nb, N, p, o, st);
@@ -1754,6 +1793,10 @@ static int dispatch(int dtype, const float* U, int64_t ldu, const void* E, const
         case 128: return launch_bf16_v2<128, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
         case 256: return launch_bf16_v2<256, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
         case 384: return launch_bf16_v2<384, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
+        case 512: return launch_bf16_v2<512, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
+        case 1024:
+          if (p.ds == 4) return launch_bf16_v2<1024, 4, WO>(U, ldu, E, enorm, nb, N, p, o, st);
+          break;
 #if HVAE_AB
         case 768: return launch_bf16_v2<768, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
 #endif
@@ -1771,6 +1814,7 @@ static int dispatch(int dtype, const float* U, int64_t ldu, const void* E, const
       case 128: return launch_f32<128, WO>(U, ldu, E, nb, N, p, o, st);
       case 256: return launch_f32<256, WO>(U, ldu, E, nb, N, p, o, st);
       case 384: return launch_f32<384, WO>(U, ldu, E, nb, N, p, o, st);
+      case 512: return launch_f32<512, WO>(U, ldu, E, nb, N, p, o, st);
       default: break;
     }
   }
@@ -1784,9 +1828,11 @@ using namespace hvae;
 
 
 extern "C" int hvae_decoder_supported(int dtype, int64_t D) {
-  if (dtype == HVAE_BF16) return D == 64 || D == 128 || D == 256 || D == 384 || (D == 768 && !dec_use_v1());
-  if (dtype == HVAE_F32) return D == 32 || D == 64 || D == 128 || D == 256 || D == 384;
-  if (dtype == HVAE_FP8) return D == 128 || D == 256 || D == 384 || D == 768;
+  // not served: fp32 at 768 / 1024 (k_dec_f32 over all of D spills), fp8 at 1024 (no three-slot ring of 64 KiB tiles)
+  if (dtype == HVAE_BF16)
+    return D == 64 || D == 128 || D == 256 || D == 384 || ((D == 512 || D == 768 || D == 1024) && !dec_use_v1());
+  if (dtype == HVAE_F32) return D == 32 || D == 64 || D == 128 || D == 256 || D == 384 || D == 512;
+  if (dtype == HVAE_FP8) return D == 128 || D == 256 || D == 384 || D == 512 || D == 768;
   return 0;
 }
 
@@ -1812,8 +1858,8 @@ extern "C" int hvae_decoder_image(int dtype, const float* E32, int64_t N, int64_
   HVAE_REQUIRE(dtype == HVAE_BF16 || dtype == HVAE_F32 || dtype == HVAE_FP8, "hvae_decoder_image: bad dtype");
   hipStream_t st = as_stream(stream);
   if (dtype == HVAE_FP8) {
-    HVAE_REQUIRE((D == 128 || D == 256 || D == 384 || D == 768) && N * D * 2 < (1ll << 31),
-                 "hvae_decoder_image: fp8 needs D in {128, 256, 384, 768} and N D < 2^30");
+    HVAE_REQUIRE((D == 128 || D == 256 || D == 384 || D == 512 || D == 768) && N * D * 2 < (1ll << 31),
+                 "hvae_decoder_image: fp8 needs D in {128, 256, 384, 512, 768} and N D < 2^30");
     const int64_t ntiles = cdiv(N, kF8TI);
     unsigned* amax = (unsigned*)((char*)out + f8_tail_offset(N, D) + 128);  // scratch word of the tail
     HVAE_HIP(hipMemsetAsync(amax, 0, sizeof(unsigned), st));

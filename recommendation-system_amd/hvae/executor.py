@@ -364,19 +364,26 @@ class FusedTrainer:
         d = lay.d
         if precision is None:
             precision = "bf16" if ops.decoder_supported(_lib.HVAE_BF16, d) else "fp32"
+
+        def refuse(name: str, dtype: int):
+            # the widths this precision's sweep is built for, as the library reports them
+            widths = [w for w in range(1, 1025) if ops.decoder_supported(dtype, w)]
+            return NotImplementedError(f"no {name} streaming decoder for embedding dim {d} "
+                                       f"(supported widths: {', '.join(map(str, widths))})")
+
         if precision == "bf16":
             if not ops.decoder_supported(_lib.HVAE_BF16, d):
-                raise NotImplementedError(f"no bf16 streaming decoder for embedding dim {d}")
+                raise refuse("bf16", _lib.HVAE_BF16)
             self.dec_dtype = _lib.HVAE_BF16
             self.E_dec = ops.decoder_image(self.E32)  # bf16 E + its tile-transposed copy
         elif precision == "fp8":
             if not ops.decoder_supported(_lib.HVAE_FP8, d):
-                raise NotImplementedError(f"no fp8 streaming decoder for embedding dim {d}")
+                raise refuse("fp8", _lib.HVAE_FP8)
             self.dec_dtype = _lib.HVAE_FP8
             self.E_dec = ops.decoder_image(self.E32, _lib.HVAE_FP8)  # bf16 E + e4m3 fragment tiles
         elif precision == "fp32":
             if not ops.decoder_supported(_lib.HVAE_F32, d):
-                raise NotImplementedError(f"no fp32 streaming decoder for embedding dim {d}")
+                raise refuse("fp32", _lib.HVAE_F32)
             self.dec_dtype = _lib.HVAE_F32
             self.E_dec = self.E32
         else:

@@ -71,7 +71,7 @@ def main():
         us = avg.value
         flops = 4.0 * args.nb * args.N * args.D
         print(json.dumps({"nb": args.nb, "N": args.N, "D": args.D, "dtype": args.dtype, "probe": args.probe,
-                          "arm": label, "launches": n.value,
+                          "train": args.train, "arm": label, "launches": n.value,
                           "avg_us": round(us, 2), "tflops": round(flops / us / 1e6, 1)}), flush=True)
 
     if not args.ab:
