@@ -590,6 +590,44 @@ int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_
                           const int32_t* col_idx, int64_t n_items, const int32_t* users, const int32_t* tests, int64_t n_rows,
                           int32_t n_neg, int32_t* out, int32_t* counts);
 
+/* ------------------------------------------------------- baselines (K17) -- */
+/* The training-free baselines of src/ml/baseline.py over the train+val matrix M [n_users, n_items]. The kernels
+ * read an item-major (CSC) image of M: col_ptr [n_items + 1], row_idx (user ids, ascending per column, every one
+ * in [0, n_users)), vals (duplicate pairs summed), and the usual CSR batch x (x->rows picks the batch's users;
+ * col_idx ascending within a row).
+ *
+ * col_sum[j] = sum_v M[v, j] in fp32, users ascending (PopularityRecommender.fit, src/ml/baseline.py:63-65:
+ * exact for counts); inv_norm[j] = 1 / ||c_j|| in double, 0 for an empty column (the column normalisation inside
+ * sklearn's cosine_similarity, :86 and :99). Either output may be NULL. */
+int hvae_csc_col_stats(const int64_t* col_ptr, const int32_t* row_idx, const float* vals, int64_t n_items,
+                       float* col_sum, double* inv_norm, void* stream);
+/* Item-KNN (ItemKNNRecommender.predict, src/ml/baseline.py:89-99; its k is never used, so no neighbour is cut):
+ *   score[b, j] = sum_{i in I_u} (c_j . c_i) / (||c_j|| ||c_i||),  u = the user of batch row b,
+ * I_u the nonzero structure of row u (not weighted by M[u, i]); an empty column contributes 0 and an empty I_u
+ * gives zeros. Computed as inv_norm[j] * sum_{v in col j} M[v, j] * T[b, v] with
+ *   T[b, v] = sum_{i in I_u} M[v, i] * inv_norm[i]
+ * in double (items and users ascending, no atomics: two runs are bitwise equal, and both scoring entry points
+ * give the same bits for the same (b, j)), rounded to fp32 once. zero_diag: leave out the i = j term (1.0 where
+ * j is in I_u), as the reference's dense path does for n_items <= 10000 (:84-87); its on-the-fly path above that
+ * keeps the term (:97-99).
+ *
+ * hvae_knn_user_weights clears T and fills it for the batch (stage 1); T is [n_users, nb] doubles, user-major,
+ * hvae_knn_workspace(nb, n_users) bytes. hvae_knn_score_candidates then scores cand [nb, C] into out [nb, C]
+ * (the 99-negative protocol of evaluate_model, :440-452; a candidate outside [0, n_items) scores NaN), and
+ * hvae_knn_scores all items into out [nb, ld] (full ranking, :453-456: the input of hvae_topk). Both read the T
+ * of the same batch x. nb <= 65535 * 256 for hvae_knn_scores. */
+size_t hvae_knn_workspace(int64_t nb, int64_t n_users);
+int hvae_knn_user_weights(const hvae_csr_batch* x, const int64_t* col_ptr, const int32_t* row_idx,
+                          const float* vals, const double* inv_norm, int64_t n_users, double* T, size_t t_bytes,
+                          void* stream);
+int hvae_knn_score_candidates(const hvae_csr_batch* x, const int64_t* col_ptr, const int32_t* row_idx,
+                              const float* vals, const double* inv_norm, int64_t n_users, const double* T,
+                              size_t t_bytes, const int32_t* cand, int64_t C, int zero_diag, float* out,
+                              void* stream);
+int hvae_knn_scores(const hvae_csr_batch* x, const int64_t* col_ptr, const int32_t* row_idx, const float* vals,
+                    const double* inv_norm, int64_t n_users, const double* T, size_t t_bytes, int zero_diag,
+                    float* out, int64_t ld, void* stream);
+
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and
  * released by hvae_host_csr_free. */

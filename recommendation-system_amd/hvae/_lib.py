@@ -179,6 +179,11 @@ SIGNATURES = {
     "hvae_topk_fused_workspace": (sz, [i64, i64, i64, i64]),
     "hvae_topk_fused": (cint, [vp, i64, vp, vp, vp, i64, i64, P(CsrBatch), i64, i64, vp, vp, vp, vp, sz,
                                vp]),
+    "hvae_csc_col_stats": (cint, [vp, vp, vp, i64, vp, vp, vp]),
+    "hvae_knn_workspace": (sz, [i64, i64]),
+    "hvae_knn_user_weights": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, vp]),
+    "hvae_knn_score_candidates": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, vp, i64, cint, vp, vp]),
+    "hvae_knn_scores": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, cint, vp, i64, vp]),
     "hvae_cast_bf16": (cint, [vp, vp, i64, vp]),
     "hvae_negatives_legacy": (cint, [vp, vp, vp, i64, vp, i64, vp, vp, i64, C.c_int32, vp, vp]),
     "hvae_read_interactions": (cint, [C.c_char_p, C.c_char_p, i64, i64, C.c_char_p, i64, i64, cint,

@@ -533,3 +533,86 @@ def negatives_legacy(indptr, indices, n_items: int, users, tests, n_neg: int, ar
     if arrays:
         return out, counts
     return [out[r, :counts[r]].astype(np.int64) for r in range(R)]
+
+
+# ---------------------------------------------------------------- baselines --
+class Csc:
+    """A device item-major (CSC) image of an interaction matrix: col_ptr int64 [N + 1], row_idx int32 (user ids
+    ascending per column), vals fp32 (duplicates summed)."""
+
+    def __init__(self, col_ptr: torch.Tensor, row_idx: torch.Tensor, vals: torch.Tensor, n_users: int, n_items: int):
+        require_hip(col_ptr, row_idx, vals)
+        assert col_ptr.dtype == torch.int64 and row_idx.dtype == torch.int32 and vals.dtype == torch.float32
+        assert col_ptr.numel() == n_items + 1 and row_idx.numel() == vals.numel()
+        self.col_ptr, self.row_idx, self.vals = col_ptr, row_idx, vals
+        self.n_users, self.n_items = int(n_users), int(n_items)
+
+
+def csc_from_scipy(mat, device) -> Csc:
+    """Upload a scipy.sparse matrix as canonical CSC (duplicates summed, user ids sorted within a column)."""
+    mat = mat.tocsc()
+    mat.sum_duplicates()
+    mat.sort_indices()
+    n_users, n_items = mat.shape
+    if mat.nnz and (int(mat.indices.min()) < 0 or int(mat.indices.max()) >= n_users):
+        raise ValueError("csc_from_scipy: a row index lies outside the matrix")
+    col_ptr = torch.as_tensor(mat.indptr.astype("int64"), device=device)
+    row = torch.as_tensor(mat.indices.astype("int32"), device=device)
+    vals = torch.as_tensor(mat.data.astype("float32"), device=device)
+    return Csc(col_ptr, row, vals, n_users, n_items)
+
+
+def csc_col_stats(m: Csc):
+    """(col_sum fp32 [N], inv_norm fp64 [N]) of a CSC image: column sums and 1 / column norms, 0 where the
+    column is empty (hvae_csc_col_stats)."""
+    dev = m.col_ptr.device
+    col_sum = torch.empty(m.n_items, dtype=torch.float32, device=dev)
+    inv_norm = torch.empty(m.n_items, dtype=torch.float64, device=dev)
+    check(lib().hvae_csc_col_stats(ptr(m.col_ptr), ptr(m.row_idx), ptr(m.vals), m.n_items, ptr(col_sum),
+                                   ptr(inv_norm), stream_of(m.col_ptr)), "hvae_csc_col_stats")
+    return col_sum, inv_norm
+
+
+def knn_workspace_bytes(nb: int, n_users: int) -> int:
+    return int(lib().hvae_knn_workspace(int(nb), int(n_users)))
+
+
+def knn_user_weights(x: Csr, m: Csc, inv_norm: torch.Tensor, T: torch.Tensor | None = None) -> torch.Tensor:
+    """Stage 1 of Item-KNN for the batch x (x.rows = its users): T [n_users, nb] fp64, cleared and filled
+    (hvae_knn_user_weights). T: a uint8 / fp64 buffer of at least knn_workspace_bytes(nb, n_users) to reuse."""
+    require_hip(inv_norm, T)
+    assert inv_norm.dtype == torch.float64 and inv_norm.numel() == m.n_items and x.n_items == m.n_items
+    need = knn_workspace_bytes(x.nb, m.n_users)
+    if T is None:
+        T = torch.empty(max(need, 8) // 8, dtype=torch.float64, device=inv_norm.device)
+    t_bytes = T.numel() * T.element_size()
+    check(lib().hvae_knn_user_weights(x.ref, ptr(m.col_ptr), ptr(m.row_idx), ptr(m.vals), ptr(inv_norm), m.n_users,
+                                      ptr(T), t_bytes, stream_of(inv_norm)), "hvae_knn_user_weights")
+    return T
+
+
+def knn_score_candidates(x: Csr, m: Csc, inv_norm: torch.Tensor, T: torch.Tensor, cand: torch.Tensor,
+                         zero_diag: bool) -> torch.Tensor:
+    """fp32 [nb, C] Item-KNN scores of cand [nb, C] int32 from the T of the same batch
+    (hvae_knn_score_candidates)."""
+    require_hip(inv_norm, T, cand)
+    assert cand.dtype == torch.int32 and cand.is_contiguous() and cand.shape[0] == x.nb
+    out = torch.empty(cand.shape, dtype=torch.float32, device=cand.device)
+    check(lib().hvae_knn_score_candidates(x.ref, ptr(m.col_ptr), ptr(m.row_idx), ptr(m.vals), ptr(inv_norm),
+                                          m.n_users, ptr(T), T.numel() * T.element_size(), ptr(cand),
+                                          cand.shape[1], int(bool(zero_diag)), ptr(out), stream_of(cand)),
+          "hvae_knn_score_candidates")
+    return out
+
+
+def knn_scores(x: Csr, m: Csc, inv_norm: torch.Tensor, T: torch.Tensor, zero_diag: bool,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """fp32 [nb, N] Item-KNN scores of every item from the T of the same batch (hvae_knn_scores)."""
+    require_hip(inv_norm, T, out)
+    if out is None:
+        out = torch.empty(x.nb, m.n_items, dtype=torch.float32, device=inv_norm.device)
+    assert out.dtype == torch.float32 and out.shape == (x.nb, m.n_items) and out.stride(1) == 1
+    check(lib().hvae_knn_scores(x.ref, ptr(m.col_ptr), ptr(m.row_idx), ptr(m.vals), ptr(inv_norm), m.n_users,
+                                ptr(T), T.numel() * T.element_size(), int(bool(zero_diag)), ptr(out),
+                                out.stride(0), stream_of(inv_norm)), "hvae_knn_scores")
+    return out

@@ -1,0 +1,171 @@
+"""`make baseline` without a GPU: the reference's CLI (src/ml/baseline.py:536-544) plus --models, the error for the
+baselines that are not served, the reference's JSON layout (:522-531), both Makefile targets (reference
+Makefile:85-93), the tie rule of the host rank helpers, and the fixture's own consistency."""
+import argparse
+import json
+import subprocess
+import sys
+from pathlib import Path
+from unittest import mock
+
+import numpy as np
+import pytest
+
+import baseline_ref as BR
+
+ROOT = Path(__file__).resolve().parent.parent
+PKG = ROOT / "recommendation-system_amd"
+
+
+def test_cli_flags_and_defaults(monkeypatch):
+    import src.ml.baseline as b
+    seen = {}
+
+    class _Stop(Exception):
+        pass
+
+    def fake_parse(self, args=None, namespace=None):
+        seen["parser"] = self
+        raise _Stop
+
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", fake_parse)
+    monkeypatch.setattr(sys, "argv", ["prog"])
+    with pytest.raises(_Stop):
+        b.main()
+    by_flag = {o: a for a in seen["parser"]._actions for o in a.option_strings}
+    assert "--data" in by_flag
+    assert by_flag["--n-negatives"].default == 99 and by_flag["--n-negatives"].type is int
+    assert by_flag["--k-values"].default == [5, 10, 20] and by_flag["--k-values"].nargs == "+"
+    assert by_flag["--models"].default == ["Popularity", "Item-KNN"] and by_flag["--models"].nargs == "+"
+
+
+@pytest.mark.parametrize("argv,want", [
+    (["--data", "d/"], ("d/", [5, 10, 20], 99, ["Popularity", "Item-KNN"])),
+    (["--data", "d/", "--n-negatives", "0", "--k-values", "3", "7"], ("d/", [3, 7], None, ["Popularity", "Item-KNN"])),
+    (["--data", "d/", "--models", "Item-KNN"], ("d/", [5, 10, 20], 99, ["Item-KNN"])),
+])
+def test_cli_passes_the_reference_arguments(argv, want):
+    import src.ml.baseline as b
+    with mock.patch.object(b, "run_all_baselines") as run, mock.patch.object(sys, "argv", ["baseline"] + argv):
+        b.main()
+    args, kw = run.call_args
+    assert args == want[:3] and kw == {"models": want[3]}
+
+
+@pytest.mark.parametrize("name", ["SVD", "Mult-VAE", "LightGCN", "Nonsense"])
+def test_unserved_models_are_an_error_that_names_the_served_ones(tmp_path, name):
+    import src.ml.baseline as b
+    with mock.patch.object(sys, "argv", ["baseline", "--data", str(tmp_path / "none"), "--models", "Popularity", name]):
+        with pytest.raises(ValueError) as e:
+            b.main()  # before any data is read: the directory does not exist
+    assert "Popularity" in str(e.value) and "Item-KNN" in str(e.value) and name in str(e.value)
+
+
+def test_recommender_api():
+    import src.ml.baseline as b
+    assert issubclass(b.PopularityRecommender, b.BaseRecommender)
+    assert issubclass(b.ItemKNNRecommender, b.BaseRecommender)
+    assert b.ItemKNNRecommender().k == 50 and b.ItemKNNRecommender(k=7).k == 7
+    with pytest.raises(TypeError):
+        b.BaseRecommender()
+    for cls in (b.PopularityRecommender, b.ItemKNNRecommender):
+        for meth in ("fit", "predict", "score_candidates", "score_all"):
+            assert callable(getattr(cls, meth))
+
+
+def test_results_json_layout(tmp_path, monkeypatch):
+    """run_all_baselines with the device work stubbed out: models in order, one timing each, the reference's file."""
+    import src.ml.baseline as b
+    from gen import write_planted_artifacts
+    data, _ = write_planted_artifacts(tmp_path, dict(n_users=30, n_items=40, d=4, n_clusters=2))
+    calls = []
+
+    def fake_eval(model, name, matrix, test_df, u2i, i2i, k_values, n_negatives):
+        calls.append((name, matrix.shape, len(test_df), tuple(k_values), n_negatives))
+        return {k: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5} for k in k_values}
+
+    monkeypatch.setattr(b.PopularityRecommender, "fit", lambda self, m: None)
+    monkeypatch.setattr(b.ItemKNNRecommender, "fit", lambda self, m: None)
+    monkeypatch.setattr(b, "evaluate_model", fake_eval)
+    res = b.run_all_baselines(str(data), [5, 10], 99)
+    assert calls == [("Popularity", (30, 40), 30, (5, 10), 99), ("Item-KNN", (30, 40), 30, (5, 10), 99)]
+    out = json.loads((tmp_path / "models" / "figures" / "baseline_results.json").read_text())
+    assert list(out) == ["Popularity", "Item-KNN"] == list(res)
+    for name in out:
+        assert list(out[name]) == ["5", "10", "training_time_seconds"]
+        assert out[name]["5"] == {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5}
+        assert isinstance(out[name]["training_time_seconds"], float)
+        assert set(res[name]) == {5, 10, "training_time_seconds"}
+
+
+def test_build_input_matrix_sums_duplicates_and_filters_positives():
+    import pandas as pd
+    import src.ml.baseline as b
+    tr = pd.DataFrame({"user_id": ["a", "a", "b"], "asin": ["x", "x", "y"], "binary_rating": [1, 1, 0]})
+    va = pd.DataFrame({"user_id": ["b"], "asin": ["x"], "binary_rating": [1]})
+    m, combined = b._build_input_matrix(tr, va, {"a": 0, "b": 1}, {"x": 0, "y": 1}, (2, 2))
+    assert m.toarray().tolist() == [[2.0, 0.0], [1.0, 0.0]] and len(combined) == 3
+
+
+@pytest.mark.parametrize("target,n_neg", [("baseline", "99"), ("baseline-full", "0")])
+def test_makefile_targets(target, n_neg):
+    r = subprocess.run(["make", "-n", "-C", str(PKG), target, "PYTHON=python", "DATA_DIR=data"], capture_output=True,
+                       text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert f"python -m src.ml.baseline --data data/ --n-negatives {n_neg}" in r.stdout.splitlines()
+
+
+def test_rank_helpers_follow_the_stable_argsort_reversed():
+    """rank_first_host: the test item after its equals; position_in_topk on a list ordered (score desc, index
+    desc). Both are candidates[np.argsort(s, kind="stable")[::-1]]."""
+    import src.ml.baseline as b
+    rng = np.random.Generator(np.random.PCG64(3))
+    for _ in range(200):
+        n = int(rng.integers(1, 40))
+        s = rng.integers(0, 4, size=n).astype(np.float32)  # few values: many ties
+        order = np.argsort(s, kind="stable")[::-1]
+        assert b.rank_first_host(s) == int(np.flatnonzero(order == 0)[0])
+        cnt = int(rng.integers(0, n))
+        order = np.argsort(s[:1 + cnt], kind="stable")[::-1]
+        assert b.rank_first_host(s, cnt) == int(np.flatnonzero(order == 0)[0])
+        t = int(rng.integers(0, n))
+        k = int(rng.integers(1, n + 1))
+        full = np.argsort(s, kind="stable")[::-1]
+        pos = b.position_in_topk(full[None, :k], np.array([t]))[0]
+        want = int(np.flatnonzero(full == t)[0])
+        assert pos == want if want < k else pos >= 2 ** 31 - 1
+        gt, eq_larger = int((s > s[t]).sum()), int(((s == s[t]) & (np.arange(n) > t)).sum())
+        assert want == gt + eq_larger
+
+
+def test_full_ranking_refuses_k_above_64():
+    import src.ml.baseline as b
+    from scipy.sparse import csr_matrix
+    with pytest.raises(ValueError, match="K <= 64"):
+        b.full_ranking_positions(None, csr_matrix((2, 100)), np.array([0]), np.array([1]), 65)
+
+
+@pytest.mark.parametrize("cfg", ["small", "large"])
+def test_fixture_reference_ranks_sit_inside_their_brackets(cfg):
+    fx = BR.fixture()
+    cand = BR.candidates(fx[f"{cfg}_tests"], fx[f"{cfg}_neg"])
+    assert cand.shape[1] == 1 + BR.N_NEG
+    pop = fx[f"{cfg}_pop"][cand]
+    knn = np.take_along_axis(fx["small_knn"], cand, axis=1) if cfg == "small" else fx["large_knn"][:, :cand.shape[1]]
+    for key, cs in (("pop", pop), ("knn", knn)):
+        gt, eq = BR.exact_bracket(cs)
+        rank = fx[f"{cfg}_{key}_rank"]
+        assert ((rank >= gt) & (rank <= gt + eq)).all()
+        assert (eq > 0).mean() == pytest.approx(BR.fixture_meta()["configs"][cfg]["tie_rows"][key])
+    for r in range(len(cand)):  # negatives: distinct, unseen, never the test item
+        assert len(set(cand[r])) == cand.shape[1]
+
+
+@pytest.mark.parametrize("cfg", ["small", "large"])
+def test_fixture_data_are_the_planted_sets(cfg):
+    matrix, users, tests = BR.planted(cfg)  # asserts the digest
+    assert list(matrix.shape) == BR.fixture_meta()["configs"][cfg]["shape"]
+    fx = BR.fixture()
+    assert np.array_equal(fx[f"{cfg}_pop"], np.asarray(matrix.sum(axis=0)).ravel())
+    seen = matrix[users[0]].indices
+    assert not np.isin(fx[f"{cfg}_neg"][0], seen).any()
