@@ -24,7 +24,6 @@ torch.cuda.CUDAGraph) and replayed:
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 from dataclasses import dataclass, field
 
@@ -60,6 +59,8 @@ class FlatLayout:
     def __init__(self, model):
         self.n_items = model.n_items
         self.hidden = list(model.hidden_dims)
+        # one hidden layer of at most 512: the shape whose encoder layer the row-parallel MLP forward can take on
+        self.one_hidden_512 = len(self.hidden) == 1 and self.hidden[0] <= 512
         self.L = model.latent_dim
         self.d = model.embedding_dim
         self.has_proj = self.L != self.d
@@ -178,6 +179,54 @@ def _sampler_order(n: int, generator: torch.Generator | None, device) -> torch.T
     return order
 
 
+@dataclass(frozen=True)
+class StepSchedule:
+    """Which arrangement of its launches one step gets (step_schedule)."""
+    rows: bool            # heads -> reparameterisation -> projection run in hvae_mlp_*_rows
+    fused_enc: bool       # ... and the first encoder layer inside that launch
+    enc_lazy: bool        # ... which reads W1t through lazy Adam itself: no catch-up launch precedes it
+    plan: str | None      # the W1 row-gradient plan: None (not training), "dp", "stream", "in_rows" or "inline"
+    catchup: str | None   # the catch-up before the forward: None, "csr", "csr_pending" or "rowgrad"
+    wgrad_side: bool      # the weight-gradient GEMMs run on the side stream
+    defer: bool           # the step records its W1t update (hvae_adam_lazy_defer) instead of applying it
+
+
+def step_schedule(*, B: int, train: bool, dp: bool, lazy_adam: bool, adam_defer: bool, enc_lazy_read: bool,
+                  rows_ok: bool, one_hidden_512: bool, side_min_batch: int, cap: int) -> StepSchedule:
+    """The one place that decides a step's arrangement, from plain values (FusedTrainer._schedule gathers them).
+
+    rows_ok: the row-parallel MLP serves this batch (FusedTrainer._mlp_rows_ok); cap: entries of the batch's row
+    gradient; side_min_batch: HVAE_PLAN_SIDE_MIN_BATCH.
+    """
+    # one hidden layer of H <= 512 with the row-parallel MLP: the encoder layer runs in hvae_mlp_fwd_rows, which
+    # can read W1t through lazy Adam itself (rows replayed in registers)
+    fused_enc = rows_ok and one_hidden_512
+    enc_lazy = train and not dp and lazy_adam and enc_lazy_read and fused_enc
+    # From side_min_batch up the plan runs on its own stream beside the catch-up, the encoder and the forward
+    # GEMMs (it needs only the batch; forking it before the catch-up: Syn-1M 1.197 -> 1.189 ms per step, Syn-10M
+    # +-0.1 %, profiles/r06_step_ab.jsonl) and the weight-gradient GEMMs run on the side stream beside the
+    # data-gradient chain (Syn-1M 1.082 -> 1.061 ms per step, Syn-10M bf16 / fp8 -0.1 / -0.3 %,
+    # profiles/r06_wgrad_side_ab.jsonl). Below it the plan is short and the CSR catch-up's dependent loads cost more
+    # than the overlap saves (All_Beauty B = 64: 0.1815 ms/step with the plan in line, 0.1965 beside; Syn-1M
+    # B = 4096: 1.545 -> 1.293 ms/step beside), and every cross-stream edge of the captured graph costs 5-10 us,
+    # more than the short kernels it would overlap.
+    big = B >= side_min_batch
+    # A deferred update pays where few of a step's rows recur in the next batch (FusedTrainer.__init__); it needs
+    # the CSR catch-up in front of the forward, so not the steps whose fused encoder reads W1t through lazy Adam.
+    defer = train and adam_defer and lazy_adam and (dp or (big and not (enc_lazy_read and fused_enc)))
+    plan = catchup = None
+    if train:
+        # "dp": the union batch's plan, on the plan stream; "in_rows": the plan fits one block, which rides in
+        # hvae_mlp_fwd_rows' launch; "inline": on the main stream in front of the forward
+        one_block = rows_ok and cap <= _lib.PLAN_SMALL_CAP and B <= _lib.PLAN_SMALL_CAP
+        plan = "dp" if dp else "stream" if big else "in_rows" if one_block else "inline"
+        if lazy_adam and not enc_lazy:
+            # the batch's rows from the plan in line before it, else from the CSR entries (no wait for the plan)
+            catchup = "rowgrad" if plan == "inline" else "csr_pending" if defer else "csr"
+    return StepSchedule(rows=rows_ok, fused_enc=fused_enc, enc_lazy=enc_lazy, plan=plan, catchup=catchup,
+                        wgrad_side=train and big, defer=defer)
+
+
 class _StepBuffers:
     """Activations / gradients for one batch size (graph-static pointers).
 
@@ -244,12 +293,43 @@ class _StepBuffers:
         for (m_, n_, k_) in gemms:
             need.append(L_.hvae_gemm_f32_workspace(m_, n_, k_))
         self.ws = torch.empty(max(int(max(need)), 256), dtype=torch.uint8, device=dev)
-        # side-stream GEMMs: their split-K slabs must not alias the main stream's
-        self.ws2 = torch.empty_like(self.ws) if ex.side is not None else None
+        # side-stream GEMMs: their split-K slabs must not alias the main stream's (as large as ws: hvae_gemm_f32
+        # clamps its split-K count by the workspace it is given, and with it the order of its sums)
+        self.ws2 = torch.empty_like(self.ws) if ex._schedule(B, train, cap).wgrad_side else None
         self.graph = None
         self.graph_k, self.graph_k_steps = None, 0  # single GPU: K consecutive steps in one graph (host-bound steps)
         self.graph_pre = self.graph_up = None  # data parallel: the CSR-packet and update graphs of a step
         self.graph_data = None  # the DeviceData a captured graph reads (held, compared by identity)
+
+
+class _Step:
+    """What the stages of one FusedTrainer._launch_fwd_bwd call share: the batch, its schedule, streams, workspaces."""
+
+    def __init__(self, ex: "FusedTrainer", bf: _StepBuffers, csr: CsrBatch, train: bool, beta: float, p_drop: float,
+                 ext: dict | None):
+        self.bf, self.csr, self.csr_ref = bf, csr, C.byref(csr)
+        self.train, self.tr, self.beta, self.p_drop = train, int(train), beta, p_drop
+        self.sched = sc = ex._schedule(bf.B, train, bf.cap)
+        if sc.wgrad_side and bf.ws2 is None:
+            raise RuntimeError("fused trainer: this buffer set was built for a schedule without the side stream")
+        self.main = torch.cuda.current_stream(ex.device)
+        self.side = ex.side if sc.wgrad_side else self.main
+        self.st, self.st2 = self.main.cuda_stream, self.side.cuda_stream
+        self.ws, self.wsn = ptr(bf.ws), bf.ws.numel()
+        self.ws2 = ptr(bf.ws2) if sc.wgrad_side else self.ws
+        self.ext = ext or {}
+        self.encm = self.ext.get("enc_masks", [None] * len(bf.h))
+        self.beta_dev = self.ks_dev = None  # (beta, beta / B) on the device in an annealed epoch (the prologue)
+        self.rows = None      # the row-parallel MLP's arguments (the forward sets them, the backward adds its own)
+
+
+def _epi_bias(b: torch.Tensor) -> Epilogue:
+    return Epilogue(kind=_lib.EPI_BIAS, bias=ptr(b))
+
+
+def _epi_rowsum(out: torch.Tensor) -> Epilogue:
+    """A weight-gradient GEMM's bias gradient = sum_k op(A)[m, k], fused into it."""
+    return Epilogue(kind=_lib.EPI_NONE, opa_rowsum=ptr(out))
 
 
 class FusedTrainer:
@@ -310,39 +390,14 @@ class FusedTrainer:
             self.pend_hdr = torch.zeros(4, dtype=torch.int64, device=device)  # PendHdr (t = 0: nothing recorded)
             self._pend = _lib.AdamPend(ptr(self.pend_slot), ptr(self.pend_item), ptr(self.pend_hdr))
             self.defer_stream = torch.cuda.Stream(device)
-        # A second stream for the optimizer-only work measured slower on MI355X: every cross-stream
-        # edge of the captured graph costs 5-10 us, more than the short kernels it overlaps. Off by
-        # default; the dependency structure stays in place for the larger configurations.
-        self.two_streams = bool(int(os.environ.get("HVAE_TWO_STREAMS", "0")))
-        # the weight-gradient GEMMs of the backward run on a second stream beside the data-gradient chain (batches
-        # from plan_side_min_batch up; the plan keeps its own stream): Syn-1M 1.082 -> 1.061 ms per step, Syn-10M
-        # bf16 / fp8 -0.1 / -0.3 % (profiles/r06_wgrad_side_ab.jsonl). HVAE_WGRAD_SIDE=0: one stream
-        self.wgrad_side = bool(int(os.environ.get("HVAE_WGRAD_SIDE", "1")))
-        self.side = torch.cuda.Stream(device) if (self.two_streams or self.wgrad_side) else None
-        # the W1-gradient plan needs only the batch: it runs on its own stream beside the forward and is joined
-        # before the row-gradient apply (the lazy-Adam catch-up then reads the batch's rows from the CSR)
-        self.plan_side = bool(int(os.environ.get("HVAE_PLAN_SIDE", "1")))
-        self.plan_stream = torch.cuda.Stream(device) if (self.plan_side and not self.two_streams) else None
-        # below this batch the plan is short and the CSR catch-up's dependent loads cost more than the overlap
-        # saves (All_Beauty B = 64: 0.1815 ms/step with the plan in line, 0.1965 beside; Syn-1M B = 4096:
-        # 1.545 -> 1.293 ms/step beside)
+        # the side stream takes the weight-gradient GEMMs of the backward, the plan stream the W1 row-gradient plan,
+        # for batches from plan_side_min_batch up (HVAE_PLAN_SIDE_MIN_BATCH; step_schedule has the measurements)
+        self.side = torch.cuda.Stream(device)
+        self.plan_stream = torch.cuda.Stream(device)
         self.plan_side_min_batch = int(os.environ.get("HVAE_PLAN_SIDE_MIN_BATCH", "512"))
-        # where the main stream joins the plan: "apply" (before the row-gradient apply, the plan overlapping the
-        # catch-up, encoder and forward GEMMs) or "fwd" (before the first forward GEMM: the plan overlaps only the
-        # catch-up and the encoder, and the forward GEMMs get every CU)
-        self.plan_join = os.environ.get("HVAE_PLAN_JOIN", "apply")
-        # when the plan forks off the main stream: "early" (before the lazy-Adam catch-up, so it overlaps the
-        # catch-up too) or "late" (after it). Syn-1M 1.197 -> 1.189 ms per step, Syn-10M 11.35-11.38 -> 11.35-11.37
-        # (profiles/r06_step_ab.jsonl); steps per graph replay 8 instead of 1 at B = 4096 changed nothing there
-        self.plan_fork = os.environ.get("HVAE_PLAN_FORK", "early")
         # batches up to MLP_ROWS_MAX_NB run the latent / projection MLP row-parallel (hvae_mlp_*_rows)
         self.mlp_rows = bool(int(os.environ.get("HVAE_MLP_ROWS", "1")))
         self._mlp_rows_cache: dict[int, bool] = {}
-        # and, when the batch's row-gradient plan fits one block, that plan as one more block of the same launch
-        self.plan_in_rows = bool(int(os.environ.get("HVAE_PLAN_IN_ROWS", "1")))
-        # the row-parallel MLP backward's LayerNorm column sums finished by the weight-gradient launch
-        # (HVAE_LN_COLS_DEFERRED=0: in the backward launch, a last-block reduction)
-        self.ln_cols_deferred = bool(int(os.environ.get("HVAE_LN_COLS_DEFERRED", "1")))
         # small batches: the fused encoder layer reads W1t through lazy Adam (HVAE_ENC_LAZY_READ=0: a catch-up launch)
         self.enc_lazy_read = bool(int(os.environ.get("HVAE_ENC_LAZY_READ", "1")))
         self.ones = torch.ones(1024, dtype=torch.float32, device=device)
@@ -551,336 +606,285 @@ class FusedTrainer:
 
     def _fork(self, src, dst):
         """dst waits for everything enqueued on src so far (a graph edge under capture)."""
-        if src is dst:
-            return
+        if src is not dst:
+            dst.wait_event(self._record(src))
+
+    def _record(self, stream) -> torch.cuda.Event:
         ev = torch.cuda.Event()
-        ev.record(src)
-        dst.wait_event(ev)
+        ev.record(stream)
+        return ev
+
+    def _schedule(self, B: int, train: bool, cap: int) -> StepSchedule:
+        """step_schedule of one step of B users, evaluated per launch: mlp_rows and lazy_adam may be set later."""
+        return step_schedule(B=B, train=train, dp=self.dp is not None, lazy_adam=self.lazy_adam,
+                             adam_defer=self.adam_defer, enc_lazy_read=self.enc_lazy_read,
+                             rows_ok=self._mlp_rows_ok(B), one_hidden_512=self.layout.one_hidden_512,
+                             side_min_batch=self.plan_side_min_batch, cap=cap)
+
+    def _defers(self, B: int) -> bool:
+        """Whether a train step of B users records its W1t update (hvae_adam_lazy_defer) instead of applying it."""
+        return self._schedule(B, True, 0).defer  # (defer does not depend on cap)
 
     def _launch_fwd_bwd(self, bf: _StepBuffers, csr: CsrBatch, train: bool, beta: float, p_drop: float,
                         ext: dict | None = None):
-        """Forward + loss (+ backward when train) of one batch.
+        """Forward + loss (+ backward when train) of one batch, in the arrangement _schedule gives it. The main
+        stream runs the dependent chain (forward, decoder, data-gradient GEMMs, LayerNorm backward, W1 row gather).
+        What only feeds the optimizer may run beside it -- the W1 row-gradient plan (needs the batch only) on the
+        plan stream, the weight-gradient GEMMs on the side stream, a recorded W1t update on the defer stream -- and
+        is joined back before the update."""
+        s = _Step(self, bf, csr, train, beta, p_drop, ext)
+        ev_plan, ev_defer = self._step_prologue(s)
+        self._step_forward(s)
+        self._step_decoder(s)
+        if not train:
+            return
+        if s.sched.defer and ev_defer is None:  # HVAE_DEFER_AT=sweep: beside the finalize and the backward
+            ev_defer = self._launch_pending(s)
+        self._step_backward(s)
+        self._step_finish(s, ev_plan, ev_defer)
 
-        Two streams: the main stream runs the dependent chain (forward, decoder,
-        data-gradient GEMMs, LayerNorm backward, W1 row gather); the side stream
-        runs what only feeds the optimizer -- the W1 row-gradient plan (needs the
-        batch only, so it overlaps the forward), the loss reduction and the
-        weight-gradient GEMMs -- and is joined back before the update.
-        """
-        L_, lay = lib(), self.layout
-        main = torch.cuda.current_stream(self.device)
-        use_side = self.side is not None and (self.two_streams or bf.B >= self.plan_side_min_batch)
-        side = self.side if use_side else main
-        st, st2 = main.cuda_stream, side.cuda_stream
-        B, H, Lt, d = bf.B, lay.hidden, lay.L, lay.d
-        ws, wsn = ptr(bf.ws), bf.ws.numel()
-        ws2 = ptr(bf.ws2) if side is not main else ws
-        seed, step = self.seed, ptr(self.step_dev)
-        tr = int(train)
-        ext = ext or {}
-        encm = ext.get("enc_masks", [None] * len(H))
-        csr_ref = C.byref(csr)
+    def _launch_pending(self, s: "_Step") -> torch.cuda.Event:
+        """The last step's recorded W1t update, for the rows this batch's catch-up did not take, on the defer
+        stream from here on. Returns the event the row-gradient apply waits for."""
+        ds = self.defer_stream
+        self._fork(s.main, ds)
+        self._apply_pending(min(self.layout.n_items, s.bf.cap), ds.cuda_stream)
+        return self._record(ds)
 
-        def gemm(ta, tb, M, N, K, A, lda, Bm, ldb, Cm, ldc, epi=None, beta_=0.0, rowsum=None, side_=False):
-            if rowsum is not None:  # bias gradient = sum_k op(A)[m, k], fused into the weight-gradient GEMM
-                epi = Epilogue(_lib.EPI_NONE, None, None, None, 0.0, None, 0, None, 0, 0, ptr(rowsum))
-            check(L_.hvae_gemm_f32(ta, tb, M, N, K, 1.0, A, lda, Bm, ldb, beta_, Cm, ldc,
-                                   C.byref(epi) if epi is not None else None, ws2 if side_ else ws, wsn,
-                                   st2 if side_ else st), "gemm")
-
-        ev_plan = None
-        dp = self.dp is not None
-        plan_in_rows = (train and not dp and not use_side and self.plan_in_rows and self._mlp_rows_ok(B)
-                        and not (self.plan_stream is not None and B >= self.plan_side_min_batch)
-                        and bf.rg.struct.cap <= _lib.PLAN_SMALL_CAP and B <= _lib.PLAN_SMALL_CAP)
-        # one hidden layer of H <= 512 with the row-parallel MLP: the encoder layer runs in hvae_mlp_fwd_rows, which
-        # can read W1t through lazy Adam itself (rows replayed in registers), so no catch-up launch precedes it
-        fused_enc = self._mlp_rows_ok(B) and len(H) == 1 and H[0] <= 512
-        enc_lazy = train and not dp and self.lazy_adam and self.enc_lazy_read and fused_enc
-        # the last step's W1t update was recorded (hvae_adam_lazy_defer): the catch-up applies it to this batch's
-        # rows, hvae_adam_lazy_pending to the rest on the defer stream
-        defer = train and self._defers(B)
-        ev_defer = None
-
-        def launch_pending():
-            nonlocal ev_defer
-            ds = self.defer_stream
-            self._fork(main, ds)
-            cfg_p = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
-            check(L_.hvae_adam_lazy_pending(C.byref(cfg_p), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
-                                            ptr(self.v), ptr(self.last_step), lay.n_items, H[0],
-                                            min(lay.n_items, bf.cap), C.byref(self._pend), ds.cuda_stream),
-                  "adam_lazy_pending")
-            ev_defer = torch.cuda.Event()
-            ev_defer.record(ds)
-
-        def catchup_csr():
-            cfg0 = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
-            if defer:
-                check(L_.hvae_adam_lazy_catchup_csr_pending(
-                    C.byref(cfg0), ptr(self.adam_tab), ptr(self.flat), ptr(self.m), ptr(self.v),
-                    ptr(self.last_step), csr_ref, H[0], C.byref(self._pend), st), "adam_lazy_catchup_csr_pending")
-            else:
-                check(L_.hvae_adam_lazy_catchup_csr(C.byref(cfg0), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
-                                                    ptr(self.v), ptr(self.last_step), csr_ref, H[0], st),
-                      "adam_lazy_catchup_csr")
+    def _step_prologue(self, s: "_Step"):
+        """What precedes the forward: the decoder's image of a trainable E, the annealed beta, and the placement of
+        the row-gradient plan, the lazy-Adam catch-up and a recorded update. Returns the events (plan, recorded
+        update) that _step_finish joins."""
+        L_, bf, sc = lib(), s.bf, s.sched
         if self.train_e:
             # E moved with the last step's Adam: the decoder's image of it and max||E|| follow (in the captured step)
             if isinstance(self.E_dec, ops.DecoderImage):
                 self.E_dec.refresh(self.E32)
             ops.row_norm_max(self.E_dec, out=self.enorm)
-        anneal = self._anneal if train else None
-        beta_dev = None
-        if anneal is not None:  # this step's (beta, beta / B) from the device schedule counter, which it advances
-            beta_dev = self.beta_dev
-            check(L_.hvae_anneal_beta(ptr(self.anneal_dev), anneal[0], anneal[1], anneal[2], B, ptr(beta_dev), st),
-                  "anneal_beta")
-        if train and dp:
-            # data parallel: no local row gradient; the union batch's plan (from the CSR packets gathered
-            # before this forward) runs on the plan stream beside it, its apply after the second exchange. The
-            # batch's W1t rows replay their deferred steps, found from the CSR entries, before the forward
-            # reads them
-            if self.lazy_adam:
-                catchup_csr()
-            if defer and self.defer_at == "fwd":
-                launch_pending()
-            ps = self.plan_stream if self.plan_stream is not None else side
-            if ps is not main:
-                self._fork(main, ps)
-                with torch.cuda.stream(ps):
-                    self.dp.merge_plan()
-                ev_plan = torch.cuda.Event()
-                ev_plan.record(ps)
-            else:
+        if not s.train:
+            return None, None
+        if self._anneal is not None:  # this step's (beta, beta / B) from the device schedule counter, which it advances
+            s.beta_dev, s.ks_dev, (b0, b1, n) = self.beta_dev, self.beta_dev[1:], self._anneal
+            check(L_.hvae_anneal_beta(ptr(self.anneal_dev), b0, b1, n, bf.B, ptr(s.beta_dev), s.st), "anneal_beta")
+        ps, ev_defer = self.plan_stream, None
+        if sc.plan in ("stream", "inline"):
+            if sc.plan == "stream":
+                # forked before the catch-up, which it then overlaps too: it reads only the batch, and the previous
+                # step's update that read the plan's buffers is behind it on the main stream
+                self._fork(s.main, ps)
+            check(L_.hvae_w1_rowgrad_plan(s.csr_ref, bf.rg.ref, ptr(bf.rg.ws), bf.rg.ws.numel(),
+                                          ps.cuda_stream if sc.plan == "stream" else s.st), "w1_rowgrad_plan")
+        # the batch's W1t rows replay their deferred steps before the forward reads them
+        if sc.catchup == "rowgrad":
+            self._catchup_rows(bf.rg.ref, s.st)
+        elif sc.catchup is not None:
+            self._catchup_csr(s.csr_ref, s.st, pending=sc.catchup == "csr_pending")
+        if sc.defer and self.defer_at == "fwd":  # beside the forward
+            ev_defer = self._launch_pending(s)
+        if sc.plan == "dp":
+            # no local row gradient: the union batch's plan, from the CSR packets gathered before this forward,
+            # runs beside it; its apply follows the second exchange
+            self._fork(s.main, ps)
+            with torch.cuda.stream(ps):
                 self.dp.merge_plan()
-        elif train and self.plan_stream is not None and B >= self.plan_side_min_batch:
-            # the batch's W1t rows replay their deferred steps (found from the CSR) before the forward reads
-            # them, while the row-gradient plan runs on the plan stream. With HVAE_PLAN_FORK=early the plan forks
-            # before the catch-up (it reads only the batch, and the previous step's update that read the plan's
-            # buffers is behind it on the main stream), so it overlaps the catch-up too
-            ps = self.plan_stream
-            early = self.plan_fork == "early"
-            if early:
-                self._fork(main, ps)
-                check(L_.hvae_w1_rowgrad_plan(csr_ref, bf.rg.ref, ptr(bf.rg.ws), bf.rg.ws.numel(), ps.cuda_stream),
-                      "w1_rowgrad_plan")
-            if self.lazy_adam and not enc_lazy:
-                catchup_csr()
-            if defer and self.defer_at == "fwd":
-                launch_pending()
-            if not early:
-                self._fork(main, ps)
-                check(L_.hvae_w1_rowgrad_plan(csr_ref, bf.rg.ref, ptr(bf.rg.ws), bf.rg.ws.numel(), ps.cuda_stream),
-                      "w1_rowgrad_plan")
-            ev_plan = torch.cuda.Event()
-            ev_plan.record(ps)
-        elif train and plan_in_rows:
-            # the plan runs as one more block of the row-parallel MLP forward's launch (hvae_mlp_fwd_rows); the
-            # batch's W1t rows replay their deferred steps, found from the CSR, before the encoder reads them
-            if self.lazy_adam and not enc_lazy:
-                cfg0 = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
-                check(L_.hvae_adam_lazy_catchup_csr(C.byref(cfg0), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
-                                                    ptr(self.v), ptr(self.last_step), csr_ref, H[0], st),
-                      "adam_lazy_catchup_csr")
-        elif train:  # the row-gradient plan depends on the batch only: overlap it with the forward
-            self._fork(main, side)
-            check(L_.hvae_w1_rowgrad_plan(csr_ref, bf.rg.ref, ptr(bf.rg.ws), bf.rg.ws.numel(), st2),
-                  "w1_rowgrad_plan")
-            if self.lazy_adam and not enc_lazy:  # the batch's W1t rows replay their deferred steps before the forward
-                cfg0 = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
-                check(L_.hvae_adam_lazy_catchup(C.byref(cfg0), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
-                                                ptr(self.v), ptr(self.last_step), bf.rg.ref, lay.n_items, H[0],
-                                                st2), "adam_lazy_catchup")
-                # the forward reads the rows this catch-up replays: it waits for it (HVAE_TWO_STREAMS=1 let the
-                # encoder start beside it)
-                self._fork(side, main)
-            if side is not main:
-                ev_plan = torch.cuda.Event()
-                ev_plan.record(side)
-        # ------------------------------------------------------ forward ---
-        rows = self._mlp_rows_args(bf, B, tr, p_drop, ext, seed) if self._mlp_rows_ok(B) else None
-        if rows is not None and len(H) == 1 and H[0] <= 512:
+        return (self._record(ps) if sc.plan in ("dp", "stream") else None), ev_defer
+
+    def _gemm(self, s: "_Step", ta, tb, M, N, K, A, lda, Bm, ldb, Cm, ldc, epi=None, side=False):
+        check(lib().hvae_gemm_f32(ta, tb, M, N, K, 1.0, A, lda, Bm, ldb, 0.0, Cm, ldc,
+                                  C.byref(epi) if epi is not None else None, s.ws2 if side else s.ws, s.wsn,
+                                  s.st2 if side else s.st), "gemm")
+
+    def _step_forward(self, s: "_Step"):
+        """Encoder, heads, reparameterisation and projection: the batch's u (and the KL rows)."""
+        L_, lay, bf, sc, P = lib(), self.layout, s.bf, s.sched, self.P
+        B, H, Lt, d = bf.B, lay.hidden, lay.L, lay.d
+        seed, step, st, encm = self.seed, ptr(self.step_dev), s.st, s.encm
+        rows = s.rows = self._mlp_rows_args(bf, B, s.tr, s.p_drop, s.ext, seed) if sc.rows else None
+        if sc.fused_enc:
             # one hidden layer: the encoder layer runs in the row-parallel MLP forward's launch below
-            rows.enc_x, rows.w1t, rows.b1 = C.pointer(csr), ptr(self.w1t), ptr(self.P["encoder.0.bias"])
-            rows.ln_w, rows.ln_b = ptr(self.P["encoder.1.weight"]), ptr(self.P["encoder.1.bias"])
+            rows.enc_x, rows.w1t, rows.b1 = C.pointer(s.csr), ptr(self.w1t), ptr(P["encoder.0.bias"])
+            rows.ln_w, rows.ln_b = ptr(P["encoder.1.weight"]), ptr(P["encoder.1.bias"])
             rows.enc_drop_mult, rows.xhat, rows.rstd = ptr(encm[0]), ptr(bf.xhat[0]), ptr(bf.rstd[0])
-            if enc_lazy:
-                self._enc_adam = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
+            if sc.enc_lazy:
+                self._enc_adam = self._adam_cfg(self.step_dev)
                 rows.adam = C.addressof(self._enc_adam)
                 rows.adam_m, rows.adam_v = ptr(self.m_w1t), ptr(self.v_w1t)
                 rows.last_step, rows.adam_tab = ptr(self.last_step), ptr(self.adam_tab)
         else:
-            check(L_.hvae_encoder_fwd(csr_ref, ptr(self.w1t), ptr(self.P["encoder.0.bias"]),
-                                      ptr(self.P["encoder.1.weight"]), ptr(self.P["encoder.1.bias"]), H[0], p_drop,
-                                      ptr(encm[0]), seed, step, tr, ptr(bf.h[0]), ptr(bf.xhat[0]),
+            check(L_.hvae_encoder_fwd(s.csr_ref, ptr(self.w1t), ptr(P["encoder.0.bias"]),
+                                      ptr(P["encoder.1.weight"]), ptr(P["encoder.1.bias"]), H[0], s.p_drop,
+                                      ptr(encm[0]), seed, step, s.tr, ptr(bf.h[0]), ptr(bf.xhat[0]),
                                       ptr(bf.rstd[0]), st), "encoder_fwd")
         for k in range(1, len(H)):
             i = 4 * k
-            W = self.P[f"encoder.{i}.weight"]
-            epi = Epilogue(_lib.EPI_BIAS, ptr(self.P[f"encoder.{i}.bias"]), None, None, 0.0, None, 0, None, 0, 0, None)
-            gemm(0, 1, B, H[k], H[k - 1], ptr(bf.h[k - 1]), H[k - 1], ptr(W), H[k - 1], ptr(bf.a[k]), H[k], epi)
-            check(L_.hvae_ln_gelu_drop_fwd(ptr(bf.a[k]), ptr(self.P[f"encoder.{i + 1}.weight"]),
-                                           ptr(self.P[f"encoder.{i + 1}.bias"]), B, H[k], p_drop, ptr(encm[k]), seed,
-                                           step, k, tr, ptr(bf.h[k]), ptr(bf.xhat[k]), ptr(bf.rstd[k]), st),
+            self._gemm(s, 0, 1, B, H[k], H[k - 1], ptr(bf.h[k - 1]), H[k - 1], ptr(P[f"encoder.{i}.weight"]),
+                       H[k - 1], ptr(bf.a[k]), H[k], _epi_bias(P[f"encoder.{i}.bias"]))
+            check(L_.hvae_ln_gelu_drop_fwd(ptr(bf.a[k]), ptr(P[f"encoder.{i + 1}.weight"]),
+                                           ptr(P[f"encoder.{i + 1}.bias"]), B, H[k], s.p_drop, ptr(encm[k]), seed,
+                                           step, k, s.tr, ptr(bf.h[k]), ptr(bf.xhat[k]), ptr(bf.rstd[k]), st),
                   "ln_gelu_drop_fwd")
-        Hl = H[-1]
-        mu, lv = bf.heads, bf.heads[:, Lt:]
-        if ev_plan is not None and self.plan_join == "fwd" and not dp:
-            main.wait_event(ev_plan)
-            ev_plan = None
         if rows is not None:
-            if plan_in_rows:
-                rows.plan_x, rows.plan_rg = C.pointer(csr), C.pointer(bf.rg.struct)
+            if sc.plan == "in_rows":  # the row-gradient plan as one more block of this launch
+                rows.plan_x, rows.plan_rg = C.pointer(s.csr), C.pointer(bf.rg.struct)
             # heads -> reparameterisation -> projection, the rows of the batch spread over blocks: one launch
             check(L_.hvae_mlp_fwd_rows(C.byref(rows), st), "mlp_fwd_rows")
-        else:
-            epi_b = Epilogue(_lib.EPI_BIAS, ptr(self.b_heads), None, None, 0.0, None, 0, None, 0, 0, None)
-            gemm(0, 1, B, 2 * Lt, Hl, ptr(bf.h[-1]), Hl, ptr(self.W_heads), Hl, ptr(bf.heads), 2 * Lt, epi_b)
-            check(L_.hvae_reparam_kl_fwd(ptr(mu), ptr(lv), 2 * Lt, B, Lt, tr, ptr(ext.get("eps")), seed, step,
-                                         ptr(bf.z), ptr(bf.eps), ptr(bf.kl_rows), st), "reparam_kl_fwd")
-        if lay.has_proj and rows is None:
-            Wa, ba = self.P["projection_layer.0.weight"], self.P["projection_layer.0.bias"]
-            Wb, bb = self.P["projection_layer.3.weight"], self.P["projection_layer.3.bias"]
-            epi1 = Epilogue(_lib.EPI_BIAS_GELU_DROP, ptr(ba), ptr(bf.p1), None, p_drop, ptr(ext.get("proj_mask")),
-                            seed, step, _lib.TAG_PROJ_DROP, tr, None)
-            gemm(0, 1, B, d, Lt, ptr(bf.z), Lt, ptr(Wa), Lt, ptr(bf.q), d, epi1)
-            epi2 = Epilogue(_lib.EPI_BIAS, ptr(bb), None, None, 0.0, None, 0, None, 0, 0, None)
-            gemm(0, 1, B, d, d, ptr(bf.q), d, ptr(Wb), d, ptr(bf.u), d, epi2)
-        if ev_plan is not None and self.plan_join == "sweep" and not dp:
-            # (HVAE_PLAN_JOIN=sweep: the plan's last kernels finish before the sweep takes every CU, instead of
-            # waiting beside it)
-            main.wait_event(ev_plan)
-            ev_plan = None
-        accum = self.accum_train if train else self.accum_val
-        # decoder sweep + finalize (split merge, sparse loss terms, du) + the batch loss means, one call
-        check(L_.hvae_decoder_train(self.dec_dtype, ptr(bf.u), d, ptr(self.E_dec), ptr(self.enorm), ptr(self.E32),
-                                    csr_ref, d, 1.0 / B, ptr(bf.lse), None, ptr(bf.recon_rows),
-                                    ptr(bf.dU) if train else None, ptr(bf.kl_rows), beta, ptr(beta_dev),
-                                    ptr(bf.loss3), ptr(accum), ws, wsn, st), "decoder_train")
-        if not train:
             return
-        if defer and ev_defer is None:  # HVAE_DEFER_AT=sweep: beside the finalize and the backward
-            launch_pending()
-        # ----------------------------------------------------- backward ---
-        G = self.G
+        Hl, mu, lv = H[-1], bf.heads, bf.heads[:, Lt:]
+        self._gemm(s, 0, 1, B, 2 * Lt, Hl, ptr(bf.h[-1]), Hl, ptr(self.W_heads), Hl, ptr(bf.heads), 2 * Lt,
+                   _epi_bias(self.b_heads))
+        check(L_.hvae_reparam_kl_fwd(ptr(mu), ptr(lv), 2 * Lt, B, Lt, s.tr, ptr(s.ext.get("eps")), seed, step,
+                                     ptr(bf.z), ptr(bf.eps), ptr(bf.kl_rows), st), "reparam_kl_fwd")
+        if lay.has_proj:
+            epi1 = Epilogue(_lib.EPI_BIAS_GELU_DROP, ptr(P["projection_layer.0.bias"]), ptr(bf.p1), None, s.p_drop,
+                            ptr(s.ext.get("proj_mask")), seed, step, _lib.TAG_PROJ_DROP, s.tr, None)
+            self._gemm(s, 0, 1, B, d, Lt, ptr(bf.z), Lt, ptr(P["projection_layer.0.weight"]), Lt, ptr(bf.q), d, epi1)
+            self._gemm(s, 0, 1, B, d, d, ptr(bf.q), d, ptr(P["projection_layer.3.weight"]), d, ptr(bf.u), d,
+                       _epi_bias(P["projection_layer.3.bias"]))
+
+    def _step_decoder(self, s: "_Step"):
+        """Decoder sweep + finalize (split merge, sparse loss terms, du) + the batch loss means: one call."""
+        bf, d = s.bf, self.layout.d
+        accum = self.accum_train if s.train else self.accum_val
+        check(lib().hvae_decoder_train(self.dec_dtype, ptr(bf.u), d, ptr(self.E_dec), ptr(self.enorm),
+                                       ptr(self.E32), s.csr_ref, d, 1.0 / bf.B, ptr(bf.lse), None,
+                                       ptr(bf.recon_rows), ptr(bf.dU) if s.train else None, ptr(bf.kl_rows), s.beta,
+                                       ptr(s.beta_dev), ptr(bf.loss3), ptr(accum), s.ws, s.wsn, s.st),
+              "decoder_train")
+
+    def _layer_bwd(self, s: "_Step", wgrad: tuple, wrowsum, xgrad: tuple, xepi=None):
+        """A layer's weight gradient (trans_a GEMM, the bias gradient = its row sums fused in) and data gradient:
+        on the side and the main stream, or with one stream both in one launch (hvae_gemm_f32_pair) -- they read
+        only finished inputs."""
+        we = _epi_rowsum(wrowsum) if wrowsum is not None else None
+        if s.side is not s.main:
+            self._fork(s.main, s.side)
+            self._gemm(s, 1, 0, *wgrad, epi=we, side=True)
+            self._gemm(s, 0, 0, *xgrad, epi=xepi)
+            return
+
+        def desc(ta, args, e):
+            M, N, K, A, lda, Bm, ldb, Cm, ldc = args
+            return GemmDesc(ta, 0, M, N, K, 1.0, A, lda, Bm, ldb, 0.0, Cm, ldc,
+                            C.pointer(e) if e is not None else None, s.ws, s.wsn)
+        dw, dx = desc(1, wgrad, we), desc(0, xgrad, xepi)
+        check(lib().hvae_gemm_f32_pair(C.byref(dw), C.byref(dx), s.st), "gemm_pair")
+
+    def _step_backward(self, s: "_Step"):
+        """Every gradient but W1t's rows: dE's dense term, the latent / projection MLP, the encoder layers."""
+        L_, lay, bf, P, G = lib(), self.layout, s.bf, self.P, self.G
+        B, H = bf.B, lay.hidden
         if self.train_e:
-            # dE's dense term (1/B) sum_b n_b softmax(u_b E^T)_i u_b in item chunks: S = u E_c^T, S <- (n_b / B)
-            # exp(S - lse_b), dE_c = S^T u (hvae_embed.hip; the sparse term follows the plan, below)
-            gE = G["item_embeddings"]
-            check(L_.hvae_csr_row_sums(csr_ref, ptr(bf.nrow), st), "csr_row_sums")
-            Cc, N_ = bf.e_chunk, lay.n_items
-            for c0 in range(0, N_, Cc):
-                cn = min(Cc, N_ - c0)
-                gemm(0, 1, B, cn, d, ptr(bf.u), d, ptr(self.E32) + 4 * c0 * d, d, ptr(bf.S), Cc)
-                check(L_.hvae_softmax_weights(ptr(bf.S), Cc, B, cn, ptr(bf.lse), ptr(bf.nrow), 1.0 / B, st),
-                      "softmax_weights")
-                gemm(1, 0, cn, d, B, ptr(bf.S), Cc, ptr(bf.u), d, ptr(gE) + 4 * c0 * d, d)
-
-        def layer_bwd(wgrad: tuple, wrowsum, xgrad: tuple, xepi=None):
-            """A layer's weight gradient (trans_a GEMM on the side stream) and data gradient: with one stream,
-            both in one launch (hvae_gemm_f32_pair) -- they read only finished inputs."""
-            if side is not main:
-                self._fork(main, side)
-                gemm(1, 0, *wgrad, rowsum=wrowsum, side_=True)
-                gemm(0, 0, *xgrad, epi=xepi)
-                return
-            we = (Epilogue(_lib.EPI_NONE, None, None, None, 0.0, None, 0, None, 0, 0, ptr(wrowsum))
-                  if wrowsum is not None else None)
-
-            def desc(ta, args, e):
-                M, N, K, A, lda, Bm, ldb, Cm, ldc = args
-                return GemmDesc(ta, 0, M, N, K, 1.0, A, lda, Bm, ldb, 0.0, Cm, ldc,
-                                C.pointer(e) if e is not None else None, ws, wsn)
-            dw, dx = desc(1, wgrad, we), desc(0, xgrad, xepi)
-            check(L_.hvae_gemm_f32_pair(C.byref(dw), C.byref(dx), st), "gemm_pair")
-
-        if rows is not None:
-            # the data gradients dp1 -> dheads -> dh of every row in one launch, then the three weight gradients
-            # (with their bias gradients) in one more
-            rows.dU, rows.dp1, rows.dheads, rows.dh = ptr(bf.dU), ptr(bf.dp1), ptr(bf.dheads), ptr(bf.dh[-1])
-            rows.ks = beta / B
-            rows.ks_dev = ptr(beta_dev[1:]) if beta_dev is not None else None
-            # with the last hidden layer's LayerNorm -> GELU -> Dropout backward (dh -> da) fused
-            kl_ = len(H) - 1
-            il = 4 * kl_
-            rows.ln_w, rows.ln_b = ptr(self.P[f"encoder.{il + 1}.weight"]), ptr(self.P[f"encoder.{il + 1}.bias"])
-            rows.xhat, rows.rstd, rows.enc_drop_mult = ptr(bf.xhat[kl_]), ptr(bf.rstd[kl_]), ptr(encm[kl_])
-            rows.enc_layer = kl_
-            ln_grads = (G[f"encoder.{il + 1}.weight"], G[f"encoder.{il + 1}.bias"], G[f"encoder.{il}.bias"])
-            rows.da = ptr(bf.da[kl_])
-            if self.ln_cols_deferred:
-                # the LayerNorm column sums stop at per-block partials in ws; the weight-gradient launch below adds
-                # them in block order (partials^T x ones), instead of an in-kernel cross-block hand-off
-                rows.d_ln_w = rows.d_ln_b = rows.d_bias = None
-            else:
-                rows.d_ln_w, rows.d_ln_b, rows.d_bias = (ptr(g) for g in ln_grads)
-            rows.ws, rows.ws_bytes = ws, wsn
-            check(L_.hvae_mlp_bwd_rows(C.byref(rows), st), "mlp_bwd_rows")
-            keep = []
-
-            def wdesc(M, N, A, lda, Bm, ldb, Cm, ldc, rowsum, K=B):
-                e = Epilogue(_lib.EPI_NONE, None, None, None, 0.0, None, 0, None, 0, 0, ptr(rowsum))
-                keep.append(e)
-                return GemmDesc(1, 0, M, N, K, 1.0, A, lda, Bm, ldb, 0.0, Cm, ldc, C.pointer(e), None, 0)
-            dl = [wdesc(d, d, ptr(bf.dU), d, ptr(bf.q), d, ptr(G["projection_layer.3.weight"]), d,
-                        G["projection_layer.3.bias"]),
-                  wdesc(d, Lt, ptr(bf.dp1), d, ptr(bf.z), Lt, ptr(G["projection_layer.0.weight"]), Lt,
-                        G["projection_layer.0.bias"]),
-                  wdesc(2 * Lt, Hl, ptr(bf.dheads), 2 * Lt, ptr(bf.h[-1]), Hl, ptr(self.gW_heads), Hl, self.gb_heads)]
-            if self.ln_cols_deferred:
-                nblk = int(L_.hvae_mlp_rows_blocks(B))
-                for kind, g in enumerate(ln_grads):  # column sums of the [blocks, 3, H] partials: partials^T ones
-                    dl.append(GemmDesc(1, 0, Hl, 1, nblk, 1.0, ws + 4 * kind * Hl, 3 * Hl,
-                                       ptr(self.ones), 1, 0.0, ptr(g), 1, None, None, 0))
-            descs = (GemmDesc * len(dl))(*dl)
-            # (on the plan stream beside the W1 row gather this ran slower: All_Beauty 0.147 vs 0.129 ms per step,
-            # profiles/r04_wgrad_beside_ab.jsonl)
-            check(L_.hvae_gemm_f32_multi(descs, len(dl), st), "gemm_multi")
-        elif lay.has_proj:
-            epi3 = Epilogue(_lib.EPI_GELU_DROP_BWD, None, None, ptr(bf.p1), p_drop, ptr(ext.get("proj_mask")), seed,
-                            step, _lib.TAG_PROJ_DROP, tr, None)
-            layer_bwd((d, d, B, ptr(bf.dU), d, ptr(bf.q), d, ptr(G["projection_layer.3.weight"]), d),
-                      G["projection_layer.3.bias"], (B, d, d, ptr(bf.dU), d, ptr(Wb), d, ptr(bf.dp1), d), epi3)
-            # dz = dp1 Wa with the reparameterisation + KL backward as its epilogue -> dheads = [dmu | dlogvar]
-            epi_r = Epilogue(_lib.EPI_REPARAM_BWD, None, None, ptr(bf.heads), 0.0, None, 0, None, 0, tr, None,
-                             ptr(bf.eps), beta / B, ptr(beta_dev[1:]) if beta_dev is not None else None)
-            layer_bwd((d, Lt, B, ptr(bf.dp1), d, ptr(bf.z), Lt, ptr(G["projection_layer.0.weight"]), Lt),
-                      G["projection_layer.0.bias"], (B, Lt, d, ptr(bf.dp1), d, ptr(Wa), Lt, ptr(bf.dheads), 2 * Lt),
-                      epi_r)
+            self._embed_bwd_dense(s)
+        if s.rows is not None:
+            self._mlp_bwd_rows(s)
         else:
-            dmu, dlv = bf.dheads, bf.dheads[:, Lt:]
-            check(L_.hvae_reparam_kl_bwd(ptr(bf.dz), ptr(mu), ptr(lv), 2 * Lt, ptr(bf.eps), B, Lt, beta / B,
-                                         ptr(beta_dev[1:]) if beta_dev is not None else None, tr,
-                                         ptr(dmu), ptr(dlv), 2 * Lt, st), "reparam_kl_bwd")
-        if rows is None:
-            layer_bwd((2 * Lt, Hl, B, ptr(bf.dheads), 2 * Lt, ptr(bf.h[-1]), Hl, ptr(self.gW_heads), Hl),
-                      self.gb_heads, (B, Hl, 2 * Lt, ptr(bf.dheads), 2 * Lt, ptr(self.W_heads), Hl, ptr(bf.dh[-1]), Hl))
+            self._mlp_bwd_gemms(s)
         for k in range(len(H) - 1, -1, -1):
             i = 4 * k
-            if not (rows is not None and k == len(H) - 1):  # (the row-parallel MLP backward did the last one)
+            if not (s.rows is not None and k == len(H) - 1):  # (the row-parallel MLP backward did the last one)
                 check(L_.hvae_ln_gelu_drop_bwd(
-                    ptr(bf.dh[k]), ptr(bf.xhat[k]), ptr(bf.rstd[k]), ptr(self.P[f"encoder.{i + 1}.weight"]),
-                    ptr(self.P[f"encoder.{i + 1}.bias"]), B, H[k], p_drop, ptr(encm[k]), seed, step, k, tr,
-                    ptr(bf.da[k]), ptr(G[f"encoder.{i + 1}.weight"]), ptr(G[f"encoder.{i + 1}.bias"]),
-                    ptr(G[f"encoder.{i}.bias"]), ws, wsn, st), "ln_gelu_drop_bwd")
+                    ptr(bf.dh[k]), ptr(bf.xhat[k]), ptr(bf.rstd[k]), ptr(P[f"encoder.{i + 1}.weight"]),
+                    ptr(P[f"encoder.{i + 1}.bias"]), B, H[k], s.p_drop, ptr(s.encm[k]), self.seed,
+                    ptr(self.step_dev), k, s.tr, ptr(bf.da[k]), ptr(G[f"encoder.{i + 1}.weight"]),
+                    ptr(G[f"encoder.{i + 1}.bias"]), ptr(G[f"encoder.{i}.bias"]), s.ws, s.wsn, s.st),
+                    "ln_gelu_drop_bwd")
             if k > 0:
-                W = self.P[f"encoder.{i}.weight"]
-                layer_bwd((H[k], H[k - 1], B, ptr(bf.da[k]), H[k], ptr(bf.h[k - 1]), H[k - 1],
-                           ptr(G[f"encoder.{i}.weight"]), H[k - 1]), None,
-                          (B, H[k - 1], H[k], ptr(bf.da[k]), H[k], ptr(W), H[k - 1], ptr(bf.dh[k - 1]), H[k - 1]))
+                self._layer_bwd(s, (H[k], H[k - 1], B, ptr(bf.da[k]), H[k], ptr(bf.h[k - 1]), H[k - 1],
+                                    ptr(G[f"encoder.{i}.weight"]), H[k - 1]), None,
+                                (B, H[k - 1], H[k], ptr(bf.da[k]), H[k], ptr(P[f"encoder.{i}.weight"]), H[k - 1],
+                                 ptr(bf.dh[k - 1]), H[k - 1]))
+
+    def _embed_bwd_dense(self, s: "_Step"):
+        """Trainable E: dE's dense term (1/B) sum_b n_b softmax(u_b E^T)_i u_b in item chunks: S = u E_c^T,
+        S <- (n_b / B) exp(S - lse_b), dE_c = S^T u (hvae_embed.hip; the sparse term follows the plan, in
+        _step_finish)."""
+        L_, bf, d, N_ = lib(), s.bf, self.layout.d, self.layout.n_items
+        B, Cc, gE = bf.B, bf.e_chunk, self.G["item_embeddings"]
+        check(L_.hvae_csr_row_sums(s.csr_ref, ptr(bf.nrow), s.st), "csr_row_sums")
+        for c0 in range(0, N_, Cc):
+            cn = min(Cc, N_ - c0)
+            self._gemm(s, 0, 1, B, cn, d, ptr(bf.u), d, ptr(self.E32) + 4 * c0 * d, d, ptr(bf.S), Cc)
+            check(L_.hvae_softmax_weights(ptr(bf.S), Cc, B, cn, ptr(bf.lse), ptr(bf.nrow), 1.0 / B, s.st),
+                  "softmax_weights")
+            self._gemm(s, 1, 0, cn, d, B, ptr(bf.S), Cc, ptr(bf.u), d, ptr(gE) + 4 * c0 * d, d)
+
+    def _mlp_bwd_rows(self, s: "_Step"):
+        """The row-parallel MLP's backward: the data gradients dp1 -> dheads -> dh of every row, with the last
+        hidden layer's LayerNorm -> GELU -> Dropout backward (dh -> da), in one launch; then the three weight
+        gradients (with their bias gradients) and the LayerNorm column sums in one more."""
+        L_, lay, bf, P, G, rows = lib(), self.layout, s.bf, self.P, self.G, s.rows
+        B, Lt, d, Hl, kl = bf.B, lay.L, lay.d, lay.hidden[-1], len(lay.hidden) - 1
+        il = 4 * kl
+        rows.dU, rows.dp1, rows.dheads, rows.dh = ptr(bf.dU), ptr(bf.dp1), ptr(bf.dheads), ptr(bf.dh[-1])
+        rows.ks, rows.ks_dev = s.beta / B, ptr(s.ks_dev)
+        rows.ln_w, rows.ln_b = ptr(P[f"encoder.{il + 1}.weight"]), ptr(P[f"encoder.{il + 1}.bias"])
+        rows.xhat, rows.rstd, rows.enc_drop_mult = ptr(bf.xhat[kl]), ptr(bf.rstd[kl]), ptr(s.encm[kl])
+        rows.enc_layer, rows.da = kl, ptr(bf.da[kl])
+        # the LayerNorm column sums stop at per-block partials in ws; the weight-gradient launch below adds them in
+        # block order (partials^T x ones), instead of an in-kernel cross-block hand-off
+        rows.d_ln_w = rows.d_ln_b = rows.d_bias = None
+        rows.ws, rows.ws_bytes = s.ws, s.wsn
+        check(L_.hvae_mlp_bwd_rows(C.byref(rows), s.st), "mlp_bwd_rows")
+        keep = []
+
+        def wdesc(M, N, A, lda, Bm, ldb, Cm, ldc, rowsum):
+            keep.append(_epi_rowsum(rowsum))
+            return GemmDesc(1, 0, M, N, B, 1.0, A, lda, Bm, ldb, 0.0, Cm, ldc, C.pointer(keep[-1]), None, 0)
+        dl = [wdesc(d, d, ptr(bf.dU), d, ptr(bf.q), d, ptr(G["projection_layer.3.weight"]), d,
+                    G["projection_layer.3.bias"]),
+              wdesc(d, Lt, ptr(bf.dp1), d, ptr(bf.z), Lt, ptr(G["projection_layer.0.weight"]), Lt,
+                    G["projection_layer.0.bias"]),
+              wdesc(2 * Lt, Hl, ptr(bf.dheads), 2 * Lt, ptr(bf.h[-1]), Hl, ptr(self.gW_heads), Hl, self.gb_heads)]
+        nblk = int(L_.hvae_mlp_rows_blocks(B))
+        for kind, g in enumerate((G[f"encoder.{il + 1}.weight"], G[f"encoder.{il + 1}.bias"], G[f"encoder.{il}.bias"])):
+            dl.append(GemmDesc(1, 0, Hl, 1, nblk, 1.0, s.ws + 4 * kind * Hl, 3 * Hl, ptr(self.ones), 1, 0.0, ptr(g),
+                               1, None, None, 0))
+        descs = (GemmDesc * len(dl))(*dl)
+        # (on the plan stream beside the W1 row gather this ran slower: All_Beauty 0.147 vs 0.129 ms per step,
+        # profiles/r04_wgrad_beside_ab.jsonl)
+        check(L_.hvae_gemm_f32_multi(descs, len(dl), s.st), "gemm_multi")
+
+    def _mlp_bwd_gemms(self, s: "_Step"):
+        """The GEMM chain's backward of projection, reparameterisation and heads: dU -> dp1 -> dheads -> dh."""
+        lay, bf, P, G = self.layout, s.bf, self.P, self.G
+        B, Lt, d, Hl = bf.B, lay.L, lay.d, lay.hidden[-1]
+        if lay.has_proj:
+            Wa, Wb = P["projection_layer.0.weight"], P["projection_layer.3.weight"]
+            epi3 = Epilogue(_lib.EPI_GELU_DROP_BWD, None, None, ptr(bf.p1), s.p_drop, ptr(s.ext.get("proj_mask")),
+                            self.seed, ptr(self.step_dev), _lib.TAG_PROJ_DROP, s.tr, None)
+            self._layer_bwd(s, (d, d, B, ptr(bf.dU), d, ptr(bf.q), d, ptr(G["projection_layer.3.weight"]), d),
+                            G["projection_layer.3.bias"], (B, d, d, ptr(bf.dU), d, ptr(Wb), d, ptr(bf.dp1), d), epi3)
+            # dz = dp1 Wa with the reparameterisation + KL backward as its epilogue -> dheads = [dmu | dlogvar]
+            epi_r = Epilogue(_lib.EPI_REPARAM_BWD, None, None, ptr(bf.heads), 0.0, None, 0, None, 0, s.tr, None,
+                             ptr(bf.eps), s.beta / B, ptr(s.ks_dev))
+            self._layer_bwd(s, (d, Lt, B, ptr(bf.dp1), d, ptr(bf.z), Lt, ptr(G["projection_layer.0.weight"]), Lt),
+                            G["projection_layer.0.bias"],
+                            (B, Lt, d, ptr(bf.dp1), d, ptr(Wa), Lt, ptr(bf.dheads), 2 * Lt), epi_r)
+        else:
+            mu, lv, dmu, dlv = bf.heads, bf.heads[:, Lt:], bf.dheads, bf.dheads[:, Lt:]
+            check(lib().hvae_reparam_kl_bwd(ptr(bf.dz), ptr(mu), ptr(lv), 2 * Lt, ptr(bf.eps), B, Lt, s.beta / B,
+                                            ptr(s.ks_dev), s.tr, ptr(dmu), ptr(dlv), 2 * Lt, s.st), "reparam_kl_bwd")
+        self._layer_bwd(s, (2 * Lt, Hl, B, ptr(bf.dheads), 2 * Lt, ptr(bf.h[-1]), Hl, ptr(self.gW_heads), Hl),
+                        self.gb_heads,
+                        (B, Hl, 2 * Lt, ptr(bf.dheads), 2 * Lt, ptr(self.W_heads), Hl, ptr(bf.dh[-1]), Hl))
+
+    def _step_finish(self, s: "_Step", ev_plan, ev_defer):
+        """Join what ran beside the main stream and gather W1t's row gradient over the plan."""
+        L_, bf, d = lib(), s.bf, self.layout.d
         if ev_plan is not None:
-            main.wait_event(ev_plan)
+            s.main.wait_event(ev_plan)
         if ev_defer is not None:  # the recorded update's rows are done before this step's apply rewrites its rows
-            main.wait_event(ev_defer)
-        if not dp:
+            s.main.wait_event(ev_defer)
+        if s.sched.plan != "dp":
             if self.train_e:
                 # dE's sparse term -(1/B) sum_b x_bi u_b over the plan's item segments (the apply with u for da),
                 # before the W1 rows take the same buffer
-                check(L_.hvae_w1_rowgrad_apply(ptr(bf.u), d, bf.rg.ref, st), "w1_rowgrad_apply(u)")
-                check(L_.hvae_rowgrad_scatter_rows(bf.rg.ref, d, -1.0 / B, ptr(G["item_embeddings"]), d, st),
-                      "rowgrad_scatter_rows")
-            check(L_.hvae_w1_rowgrad_apply(ptr(bf.da[0]), H[0], bf.rg.ref, st), "w1_rowgrad_apply")
-        self._fork(side, main)  # join: every gradient is complete on the main stream
+                check(L_.hvae_w1_rowgrad_apply(ptr(bf.u), d, bf.rg.ref, s.st), "w1_rowgrad_apply(u)")
+                check(L_.hvae_rowgrad_scatter_rows(bf.rg.ref, d, -1.0 / bf.B, ptr(self.G["item_embeddings"]), d,
+                                                   s.st), "rowgrad_scatter_rows")
+            check(L_.hvae_w1_rowgrad_apply(ptr(bf.da[0]), self.layout.hidden[0], bf.rg.ref, s.st),
+                  "w1_rowgrad_apply")
+        self._fork(s.side, s.main)  # join: every gradient is complete on the main stream
 
     def _mlp_rows_ok(self, B: int) -> bool:
         """The row-parallel latent / projection MLP (hvae_mlp_fwd_rows / _bwd_rows) serves this batch:
@@ -891,10 +895,8 @@ class FusedTrainer:
             return False
         ok = self._mlp_rows_cache.get(B)
         if ok is None:  # the library's own shape rules (rows per block, LDS of both directions), asked for the
-            # configuration the step launches: the fused encoder layer (one hidden layer of at most 512) needs its
-            # own LDS beside the MLP's
-            fused_enc = int(len(lay.hidden) == 1 and lay.hidden[0] <= 512)
-            ok = bool(lib().hvae_mlp_rows_supported(B, lay.hidden[-1], lay.L, lay.d, fused_enc))
+            # configuration the step launches: the fused encoder layer needs its own LDS beside the MLP's
+            ok = bool(lib().hvae_mlp_rows_supported(B, lay.hidden[-1], lay.L, lay.d, int(lay.one_hidden_512)))
             self._mlp_rows_cache[B] = ok
         return ok
 
@@ -910,82 +912,74 @@ class FusedTrainer:
             kl_rows=ptr(bf.kl_rows), p1=ptr(bf.p1), q=ptr(bf.q), u=ptr(bf.u))
 
     def _launch_update(self, rg, bf: _StepBuffers, advance: int = 0):
-        """clip_grad_norm_(5.0) + Adam over the flat state: two launches.
-
-        The clip launch also advances the step counter (and the batch offset);
-        Adam reads the pre-increment step from step_snap.
-        """
+        """clip_grad_norm_(5.0) + Adam over the flat state: two launches. The clip launch also advances the step
+        counter (and the batch offset); Adam reads the pre-increment step from step_snap."""
         L_, lay = lib(), self.layout
         st = torch.cuda.current_stream(self.device).cuda_stream
-        H = lay.hidden
-        ws, wsn = ptr(bf.ws), bf.ws.numel()
-        cfg = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_snap, self.coef)
-        if self.lazy_adam:  # the clip's last block also writes the step's Adam scalars into the step table
-            check(L_.hvae_clip_grad_norm_step_adam(ptr(self.g_small), lay.n_small, rg.ref, H[0], self.max_norm,
-                                                   ptr(self.norm), ptr(self.coef), ptr(self.step_dev),
-                                                   ptr(self.step_snap), ptr(self.boff) if advance else None, advance,
-                                                   C.byref(cfg), ptr(self.adam_tab), ws, wsn, st),
-                  "clip_grad_norm_step_adam")
-        else:
-            check(L_.hvae_clip_grad_norm_step(ptr(self.g_small), lay.n_small, rg.ref, H[0], self.max_norm,
-                                              ptr(self.norm), ptr(self.coef), ptr(self.step_dev),
-                                              ptr(self.step_snap), ptr(self.boff) if advance else None, advance,
-                                              ws, wsn, st), "clip_grad_norm_step")
-        # W1t (row-sparse gradient, offset 0 of the flat buffer) and the dense segment in one launch
-        if self.lazy_adam and self._defers(bf.B):  # W1t's rows recorded, moved by the next step (or a flush)
-            check(L_.hvae_adam_lazy_defer(C.byref(cfg), ptr(self.adam_tab), self.tab_len, ptr(self.flat),
-                                          ptr(self.m), ptr(self.v), ptr(self.last_step), rg.ref, H[0],
-                                          ptr(self.g_small), lay.small_offset, lay.n_small, C.byref(self._pend), st),
-                  "adam_lazy_defer")
-            self._pend_open = True
-        elif self.lazy_adam:
-            check(L_.hvae_adam_lazy(C.byref(cfg), ptr(self.adam_tab), self.tab_len, ptr(self.flat), ptr(self.m),
-                                    ptr(self.v), ptr(self.last_step), rg.ref, H[0], ptr(self.g_small),
-                                    lay.small_offset, lay.n_small, st), "adam_lazy")
-        else:
+        H0, ws, wsn = lay.hidden[0], ptr(bf.ws), bf.ws.numel()
+        cfg = self._adam_cfg(self.step_snap, self.coef)
+        clip = (ptr(self.g_small), lay.n_small, rg.ref, H0, self.max_norm, ptr(self.norm), ptr(self.coef),
+                ptr(self.step_dev), ptr(self.step_snap), ptr(self.boff) if advance else None, advance)
+        if not self.lazy_adam:
+            check(L_.hvae_clip_grad_norm_step(*clip, ws, wsn, st), "clip_grad_norm_step")
             check(L_.hvae_adam_flat(C.byref(cfg), ptr(self.flat), ptr(self.m), ptr(self.v), rg.ref, lay.n_items,
-                                    H[0], ptr(self.g_small), lay.small_offset, lay.n_small, st), "adam_flat")
+                                    H0, ptr(self.g_small), lay.small_offset, lay.n_small, st), "adam_flat")
+            return
+        # the clip's last block also writes the step's Adam scalars into the step table
+        check(L_.hvae_clip_grad_norm_step_adam(*clip, C.byref(cfg), ptr(self.adam_tab), ws, wsn, st),
+              "clip_grad_norm_step_adam")
+        # W1t (row-sparse gradient, offset 0 of the flat buffer) and the dense segment in one launch
+        lazy = (C.byref(cfg), ptr(self.adam_tab), self.tab_len, ptr(self.flat), ptr(self.m), ptr(self.v),
+                ptr(self.last_step), rg.ref, H0, ptr(self.g_small), lay.small_offset, lay.n_small)
+        if self._defers(bf.B):  # W1t's rows recorded, moved by the next step (or a flush)
+            check(L_.hvae_adam_lazy_defer(*lazy, C.byref(self._pend), st), "adam_lazy_defer")
+            self._pend_open = True
+        else:
+            check(L_.hvae_adam_lazy(*lazy, st), "adam_lazy")
+
+    def _adam_cfg(self, step: torch.Tensor, coef: torch.Tensor | None = None) -> _lib.Adam:
+        """The optimizer's constants with the device step counter (and clip coefficient) a launch reads."""
+        return ops.adam_config(self.lr, self.betas, self.eps, self.wd, step, coef)
+
+    def _lazy_w1(self) -> tuple:
+        """The leading arguments of the lazy-Adam catch-up calls: the constants at the current step, the step
+        table, and W1t's parameters, moments and per-row step stamps."""
+        return (C.byref(self._adam_cfg(self.step_dev)), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
+                ptr(self.v), ptr(self.last_step))
+
+    def _catchup_csr(self, csr_ref, st, pending: bool):
+        """The batch's W1t rows, found from its CSR entries, replay the steps they sat out; pending: after taking
+        the last step's recorded update (hvae_adam_lazy_defer), which hvae_adam_lazy_pending moves for the rest."""
+        H0 = self.layout.hidden[0]
+        if pending:
+            check(lib().hvae_adam_lazy_catchup_csr_pending(*self._lazy_w1(), csr_ref, H0, C.byref(self._pend), st),
+                  "adam_lazy_catchup_csr_pending")
+        else:
+            check(lib().hvae_adam_lazy_catchup_csr(*self._lazy_w1(), csr_ref, H0, st), "adam_lazy_catchup_csr")
+
+    def _catchup_rows(self, rg_ref, st):
+        """The same for the rows of a finished row-gradient plan (rg_ref None: every row)."""
+        check(lib().hvae_adam_lazy_catchup(*self._lazy_w1(), rg_ref, self.layout.n_items, self.layout.hidden[0],
+                                           st), "adam_lazy_catchup")
+
+    def _apply_pending(self, sweep_rows: int, st):
+        check(lib().hvae_adam_lazy_pending(*self._lazy_w1(), self.layout.n_items, self.layout.hidden[0], sweep_rows,
+                                           C.byref(self._pend), st), "adam_lazy_pending")
 
     def flush(self):
-        """Bring every W1t row (and its m, v) up to the completed step count (lazy Adam).
-
-        Called at the end of every epoch and eager step, so that whatever reads the
-        parameters or the optimizer state next sees torch's values.
-        """
+        """Bring every W1t row (and its m, v) up to the completed step count (lazy Adam). Called at the end of every
+        epoch and eager step, so that whatever reads the parameters or the optimizer state next sees torch's values."""
         if not self.lazy_adam:
             return
         self._resolve_pending()
-        cfg0 = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
-        check(lib().hvae_adam_lazy_catchup(C.byref(cfg0), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
-                                           ptr(self.v), ptr(self.last_step), None, self.layout.n_items,
-                                           self.layout.hidden[0], torch.cuda.current_stream(self.device).cuda_stream),
-              "adam_lazy_flush")
-
-    def _defers(self, B: int) -> bool:
-        """Whether a train step of B users records its W1t update (hvae_adam_lazy_defer) instead of applying it:
-        the steps whose forward is preceded by the CSR catch-up and whose plan runs on its own stream (data
-        parallel, or B >= plan_side_min_batch), not the small batches whose fused encoder reads W1t through lazy
-        Adam itself."""
-        if not (self.adam_defer and self.lazy_adam) or self.two_streams:  # (lazy_adam may be switched off later)
-            return False
-        if self.dp is not None:
-            return True
-        if self.plan_stream is None or B < self.plan_side_min_batch:
-            return False
-        H = self.layout.hidden
-        return not (self.enc_lazy_read and self._mlp_rows_ok(B) and len(H) == 1 and H[0] <= 512)
+        self._catchup_rows(None, torch.cuda.current_stream(self.device).cuda_stream)
 
     def _resolve_pending(self):
         """Apply a recorded W1t update still pending, on the current stream (eager; a no-op on the device when
         the next step's catch-up and hvae_adam_lazy_pending already did)."""
         if not self._pend_open:
             return
-        lay = self.layout
-        cfg0 = ops.adam_config(self.lr, self.betas, self.eps, self.wd, self.step_dev, None)
-        check(lib().hvae_adam_lazy_pending(C.byref(cfg0), ptr(self.adam_tab), ptr(self.flat), ptr(self.m),
-                                           ptr(self.v), ptr(self.last_step), lay.n_items, lay.hidden[0],
-                                           lay.n_items, C.byref(self._pend),
-                                           torch.cuda.current_stream(self.device).cuda_stream), "adam_lazy_pending")
+        self._apply_pending(self.layout.n_items, torch.cuda.current_stream(self.device).cuda_stream)
         self._pend_open = False
 
     def _hyper(self) -> tuple:
