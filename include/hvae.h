@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define HVAE_ABI_VERSION 5
+#define HVAE_ABI_VERSION 6
 
 enum {
   HVAE_OK = 0,
@@ -232,6 +232,27 @@ typedef struct hvae_gemm_desc {
  * runs for each nn.Linear of model.py:100-155 in backward). Other pairings run as two
  * hvae_gemm_f32 launches. Split-K problems need distinct workspaces. */
 int hvae_gemm_f32_pair(const hvae_gemm_desc* w, const hvae_gemm_desc* x, void* stream);
+
+/* Which kernel instance a launch runs (ABI 6). Host arithmetic only: no HIP call, no allocation, the operand
+ * addresses are read for their 16-byte alignment alone, and it answers on a machine without a GPU. The launchers
+ * run from the same plan, so the answer is what hvae_gemm_f32 / hvae_gemm_f32_pair launch for these arguments.
+ * bm = bn = 0: an empty product (M or N = 0), nothing is launched. */
+typedef struct hvae_gemm_plan {
+  int family;      /* 0 register-staged, 1 fast, 2 LDS-DMA */
+  int bm, bn;      /* block tile */
+  int splits;      /* k ranges (1 = no split-K) */
+  int64_t kps;     /* k per split */
+  int nst;         /* register-staged: the instance, 12, 4 or 1; otherwise 0 */
+  int long_k;      /* register-staged: 1 when the k range exceeds the instance's up-front stages (streams) */
+  int vec_a, vec_b; /* 16-byte operand loads proven safe (aligned base, leading dimension a multiple of 4) */
+} hvae_gemm_plan;
+int hvae_gemm_f32_plan(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
+                       const float* A, int64_t lda, const float* B, int64_t ldb,
+                       int has_ws, size_t ws_bytes, hvae_gemm_plan* out);
+/* launch_kind: 0 two launches, 1 k_gemm_dma_pair, 2 k_gemm_mixed_pair, 3 k_gemm_f32_pair; out[0] = w, out[1] = x
+ * (for 0 each half's own hvae_gemm_f32 plan; k_gemm_f32_pair has the staging classes 12 and 4 only) */
+int hvae_gemm_f32_pair_plan(const hvae_gemm_desc* w, const hvae_gemm_desc* x,
+                            hvae_gemm_plan out[2], int* launch_kind);
 
 /* out[n] = beta * out[n] + sum_m X[m, n]  (bias gradients; deterministic) */
 int hvae_colsum(const float* X, int64_t M, int64_t N, int64_t ldx, float beta, float* out,

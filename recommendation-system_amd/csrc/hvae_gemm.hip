@@ -1009,16 +1009,17 @@ struct FastPlan {
 // 38.8 at best); so do batches under 1024 (K = B). Tile: 32 x 32 while that gives <= 256 tiles, else 64 x 64.
 // A/B knobs, read at every call: HVAE_GEMM_FAST=0 (register-staged kernel only), HVAE_GEMM_FAST_TILE=32|64,
 // HVAE_GEMM_FAST_SPLITS=s
-static FastPlan fast_plan(bool ta, bool tb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
-                          const float* B, int64_t ldb, bool /*pair_w*/) {
+static FastPlan fast_plan(bool ta, bool tb, int64_t M, int64_t N, int64_t K, uintptr_t A, int64_t lda,
+                          uintptr_t B, int64_t ldb) {
   FastPlan f;
+  if (M <= 0 || N <= 0) return f;  // an empty product (hvae_gemm_f32_workspace asks for any shape): no tiles to count
   const char* e = ab_getenv("HVAE_GEMM_FAST");
   if (e && std::atoi(e) == 0) return f;
   if (!ta) {
     // HVAE_GEMM_FAST_SHORT=1 (A/B): the batch GEMMs (x W^T, x W; K = d, H or 2L) on the fast path too, one k range
     const char* fs = ab_getenv("HVAE_GEMM_FAST_SHORT");
     if (!fs || std::atoi(fs) == 0) return f;
-    if (K % FBK || ((uintptr_t)A) % 16 || ((uintptr_t)B) % 16 || lda % 4 || ldb % 4) return f;
+    if (K % FBK || A % 16 || B % 16 || lda % 4 || ldb % 4) return f;
     int bt = cdiv(M, 64) * cdiv(N, 64) >= 256 ? 64 : 32;
     if (const char* t = ab_getenv("HVAE_GEMM_FAST_TILE")) bt = std::atoi(t) == 64 ? 64 : 32;
     if (M % bt || N % bt) return f;
@@ -1028,7 +1029,7 @@ static FastPlan fast_plan(bool ta, bool tb, int64_t M, int64_t N, int64_t K, con
     return f;
   }
   if (tb) return f;
-  if (K < 1024 || K % FBK || ((uintptr_t)A) % 16 || ((uintptr_t)B) % 16 || lda % 4 || ldb % 4) return f;
+  if (K < 1024 || K % FBK || A % 16 || B % 16 || lda % 4 || ldb % 4) return f;
   int bt = cdiv(M, 32) * cdiv(N, 32) <= 256 ? 32 : 64;
   if (const char* t = ab_getenv("HVAE_GEMM_FAST_TILE")) bt = std::atoi(t) == 64 ? 64 : 32;
   if (M % bt || N % bt) return f;
@@ -1051,18 +1052,27 @@ static FastPlan fast_plan(bool ta, bool tb, int64_t M, int64_t N, int64_t K, con
 // or kTile6432 (64 x 32, single launches only). A/B knobs (read at every call): HVAE_GEMM_DMA=0 keeps the
 // register-staged / fast kernels, HVAE_GEMM_DMA_TILE=32|64|6432 forces a tile.
 constexpr int kTile6432 = 6432;
-static int dma_tile(bool ta, bool tb, const GemmP& g, bool pair = false) {
+// One problem as the planner sees it: numbers only.
+struct PlanArgs {
+  bool ta, tb;
+  int64_t M, N, K;
+  uintptr_t A; int64_t lda;  // operand addresses: only their alignment is read
+  uintptr_t B; int64_t ldb;
+  bool has_ws; size_t ws_bytes;
+};
+// (kps, splits: the problem's k ranges as planned before the family is chosen)
+static int dma_tile(const PlanArgs& p, int64_t kps, int splits, bool pair) {
   if (const char* e = ab_getenv("HVAE_GEMM_DMA"))
     if (std::atoi(e) == 0) return 0;
-  const int64_t M = g.M, N = g.N, K = g.K;
-  if (K == 0 || K % FBK || g.kps % FBK || ((uintptr_t)g.A) % 16 || ((uintptr_t)g.B) % 16 || g.lda % 4 || g.ldb % 4)
-    return 0;
-  const int64_t ea = (ta ? K * g.lda : M * g.lda) * 4, eb = (tb ? N * g.ldb : K * g.ldb) * 4;
+  const bool ta = p.ta, tb = p.tb;
+  const int64_t M = p.M, N = p.N, K = p.K;
+  if (K == 0 || K % FBK || kps % FBK || p.A % 16 || p.B % 16 || p.lda % 4 || p.ldb % 4) return 0;
+  const int64_t ea = (ta ? K * p.lda : M * p.lda) * 4, eb = (tb ? N * p.ldb : K * p.ldb) * 4;
   if (ea >= ((int64_t)1 << 31) || eb >= ((int64_t)1 << 31)) return 0;  // 32-bit buffer offsets
   // 64 x 64 from two blocks per CU; 64 x 32 where that doubles one block per CU to two; else 64 x 64 at one
   // block per CU; else 32 x 32
-  const int64_t t64 = (M % 64 == 0 && N % 64 == 0) ? (M / 64) * (N / 64) * (int64_t)g.gz : 0;
-  const int64_t t6432 = (M % 64 == 0 && N % 32 == 0) ? (M / 64) * (N / 32) * (int64_t)g.gz : 0;
+  const int64_t t64 = (M % 64 == 0 && N % 64 == 0) ? (M / 64) * (N / 64) * (int64_t)splits : 0;
+  const int64_t t6432 = (M % 64 == 0 && N % 32 == 0) ? (M / 64) * (N / 32) * (int64_t)splits : 0;
   int bt = t64 >= 512 ? 64 : (!pair && !ta && t6432 >= 512) ? kTile6432 : t64 >= 256 ? 64 : 32;
   if (const char* e = ab_getenv("HVAE_GEMM_DMA_TILE")) {
     const int v = std::atoi(e);
@@ -1070,7 +1080,7 @@ static int dma_tile(bool ta, bool tb, const GemmP& g, bool pair = false) {
   }
   const int bm = bt == kTile6432 ? 64 : bt, bn = bt == kTile6432 ? 32 : bt;
   if (M % bm || N % bn) return 0;
-  if (g.slab && (M / bm) * (N / bn) > (int64_t)kTicketSlice) return 0;
+  if (splits > 1 && (M / bm) * (N / bn) > (int64_t)kTicketSlice) return 0;  // (split-K: one ticket per tile)
   // the weight gradients in 32-square tiles (768 x 128, 256 x 512 over K = 4096) stay on the fast path: 20.5 /
   // 21.3 us there against 23.0 / 26.9 here (profiles/r05_gemm_dma_trace_ab.jsonl)
   if (ta && !tb && bt == 32 && !ab_getenv("HVAE_GEMM_DMA_TILE")) return 0;
@@ -1078,6 +1088,101 @@ static int dma_tile(bool ta, bool tb, const GemmP& g, bool pair = false) {
 }
 
 static int colsum_parts(int64_t M) { return (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(M, 64), 64)); }
+
+// ---- the plan of one problem: which kernel family, tile, k ranges and staging class a launch runs. Host
+// arithmetic on numbers only (hvae_gemm_f32_plan answers from it; every launcher below runs from it, so the query
+// cannot drift from the launch). bm = bn = 0: an empty product, nothing is launched.
+// pair: as one half of a fused pair launch (square LDS-DMA tiles only).
+static hvae_gemm_plan plan_one(const PlanArgs& p, bool pair) {
+  hvae_gemm_plan o{};
+  o.splits = 1;
+  if (p.M <= 0 || p.N <= 0) return o;
+  const int64_t M = p.M, N = p.N, K = p.K;
+  const FastPlan f = fast_plan(p.ta, p.tb, M, N, K, p.A, p.lda, p.B, p.ldb);
+  int splits = f.bm ? f.splits : gemm_splits(M, N, K);
+  if (splits > 1) {
+    const int64_t fit = p.has_ws ? (int64_t)(p.ws_bytes / ((size_t)(M * N + M) * sizeof(float))) : 0;
+    splits = (int)std::min<int64_t>(splits, fit);
+    if (splits < 2) splits = 1;
+  }
+  int64_t kps = K;
+  if (splits > 1) {
+    kps = cdiv(cdiv(K, splits), GBK) * GBK;
+    splits = (int)cdiv(K, kps);
+  }
+  o.splits = std::max(splits, 1);
+  o.kps = (K <= 0) ? 0 : kps;
+  o.vec_a = (p.A % 16 == 0) && (p.lda % 4 == 0);
+  o.vec_b = (p.B % 16 == 0) && (p.ldb % 4 == 0);
+  if (const int dt = dma_tile(p, o.kps, o.splits, pair)) {
+    o.family = 2;
+    o.bm = dt == kTile6432 ? 64 : dt;
+    o.bn = dt == kTile6432 ? 32 : dt;
+  } else if (f.bm) {
+    o.family = 1;
+    o.bm = f.bm;
+    o.bn = f.bn;
+  } else {
+    o.family = 0;
+    o.bm = o.bn = gemm_tile(M, N, K);
+    o.nst = nst_class(p.ta, p.tb, o.kps);
+    o.long_k = cdiv(o.kps, GBK) > o.nst;
+  }
+  return o;
+}
+
+// One problem of hvae_gemm_f32_multi: always the 32-square ring instance over one k range.
+static hvae_gemm_plan plan_multi(const PlanArgs& p) {
+  hvae_gemm_plan o{};
+  o.splits = 1;
+  if (p.M <= 0 || p.N <= 0) return o;
+  o.bm = o.bn = 32;
+  o.kps = std::max<int64_t>(p.K, 0);
+  o.nst = kRingStages;
+  o.long_k = cdiv(o.kps, GBK) > o.nst;
+  o.vec_a = (p.A % 16 == 0) && (p.lda % 4 == 0);
+  o.vec_b = (p.B % 16 == 0) && (p.ldb % 4 == 0);
+  return o;
+}
+
+static PlanArgs plan_args(const hvae_gemm_desc& d) {
+  return PlanArgs{d.trans_a != 0, d.trans_b != 0, d.M, d.N, d.K, (uintptr_t)d.A, d.lda, (uintptr_t)d.B, d.ldb,
+                  d.ws != nullptr, d.ws_bytes};
+}
+
+// hvae_gemm_f32_pair's launch: 0 two hvae_gemm_f32 launches (out: each half's own plan), 1 k_gemm_dma_pair,
+// 2 k_gemm_mixed_pair, 3 k_gemm_f32_pair (out: the halves as the fused kernel runs them). One launch serves the
+// (A^T B, A B) pair of a layer's backward; any other pairing runs as two launches.
+static int plan_pair(const hvae_gemm_desc& w, const hvae_gemm_desc& x, hvae_gemm_plan out[2]) {
+  const PlanArgs pw = plan_args(w), px = plan_args(x);
+  const auto two = [&] {
+    out[0] = plan_one(pw, false);
+    out[1] = plan_one(px, false);
+    return 0;
+  };
+  const bool shared_ws = w.ws && w.ws == x.ws && gemm_splits(w.M, w.N, w.K) > 1 &&
+                         gemm_splits(x.M, x.N, x.K) > 1;  // both split-K into one slab: two launches
+  const bool fused = w.trans_a && !w.trans_b && !x.trans_a && !x.trans_b && w.M > 0 && w.N > 0 && x.M > 0 &&
+                     x.N > 0 && !shared_ws;
+  if (!fused) return two();
+  const hvae_gemm_plan p0 = plan_one(pw, true), p1 = plan_one(px, true);
+  const bool both_split = p0.splits > 1 && p1.splits > 1;
+  const bool d0 = p0.family == 2, d1 = p1.family == 2;
+  // one half on the LDS-DMA path, the other not: two launches, so that each half runs the kernel its own
+  // hvae_gemm_f32 call would (the pair stays bitwise the two launches)
+  if (d0 != d1 || (d0 && d1 && both_split)) return two();
+  out[0] = p0;
+  out[1] = p1;
+  if (d0 && d1) return 1;
+  if (p0.family == 1 || p1.family == 1) {
+    if (p0.family != 1 || p1.family == 1 || both_split) return two();  // not (fast dW, register-staged dX)
+    return 2;
+  }
+  // (the register-staged pair keeps two classes: long k ranges on the kRegStages instance's one-tile lookahead)
+  for (int i = 0; i < 2; ++i)
+    if (out[i].nst != kRingStages) out[i].nst = kRegStages;
+  return 3;
+}
 
 }  // namespace hvae
 
@@ -1087,19 +1192,39 @@ extern "C" size_t hvae_gemm_f32_workspace(int64_t M, int64_t N, int64_t K) {
   int s = gemm_splits(M, N, K);
   // the fast path's split count (operands assumed aligned; as a pair's weight-gradient half or alone)
   static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int pw = 0; pw < 2; ++pw)
-    for (int ta = 0; ta < 2; ++ta) {
-      const FastPlan f = fast_plan(ta, false, M, N, K, dummy, 4, dummy, 4, pw);
-      if (f.bm) s = std::max(s, f.splits);
-    }
+  for (int ta = 0; ta < 2; ++ta) {
+    const FastPlan f = fast_plan(ta, false, M, N, K, (uintptr_t)dummy, 4, (uintptr_t)dummy, 4);
+    if (f.bm) s = std::max(s, f.splits);
+  }
   return s > 1 ? (size_t)s * (M * N + M) * sizeof(float) : 0;
 }
 
-// Validate one problem and fill its launch record (tile size in *bt).
-static int gemm_setup(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, float alpha, const float* A,
+extern "C" int hvae_gemm_f32_plan(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, const float* A,
+                                  int64_t lda, const float* B, int64_t ldb, int has_ws, size_t ws_bytes,
+                                  hvae_gemm_plan* out) {
+  HVAE_REQUIRE(M >= 0 && N >= 0 && K >= 0 && out, "hvae_gemm_f32_plan: bad shape / null out");
+  HVAE_REQUIRE(M < (1ll << 31) / 64 * 64 && N < (1ll << 31), "hvae_gemm_f32_plan: too large");
+  *out = plan_one(PlanArgs{trans_a != 0, trans_b != 0, M, N, K, (uintptr_t)A, lda, (uintptr_t)B, ldb, has_ws != 0,
+                           ws_bytes},
+                  false);
+  return HVAE_OK;
+}
+
+extern "C" int hvae_gemm_f32_pair_plan(const hvae_gemm_desc* w, const hvae_gemm_desc* x, hvae_gemm_plan out[2],
+                                       int* launch_kind) {
+  HVAE_REQUIRE(w && x && out && launch_kind, "hvae_gemm_f32_pair_plan: null argument");
+  for (const hvae_gemm_desc* d : {w, x}) {
+    HVAE_REQUIRE(d->M >= 0 && d->N >= 0 && d->K >= 0, "hvae_gemm_f32_pair_plan: bad shape");
+    HVAE_REQUIRE(d->M < (1ll << 31) / 64 * 64 && d->N < (1ll << 31), "hvae_gemm_f32_pair_plan: too large");
+  }
+  *launch_kind = plan_pair(*w, *x, out);
+  return HVAE_OK;
+}
+
+// Validate one problem and fill its launch record, all but what the plan decides (gemm_apply_plan).
+static int gemm_check(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K, float alpha, const float* A,
                       int64_t lda, const float* B, int64_t ldb, float beta, float* C, int64_t ldc,
-                      const hvae_epilogue* epi, void* ws, size_t ws_bytes, GemmP& g, int& bt,
-                      FastPlan* fp = nullptr, bool pair_w = false) {
+                      const hvae_epilogue* epi, GemmP& g) {
   HVAE_REQUIRE(M >= 0 && N >= 0 && K >= 0 && C, "hvae_gemm_f32: bad shape / null C");
   HVAE_REQUIRE(ldc >= N, "hvae_gemm_f32: ldc < N");
   HVAE_REQUIRE(M < (1ll << 31) / 64 * 64 && N < (1ll << 31), "hvae_gemm_f32: too large");
@@ -1131,33 +1256,20 @@ static int gemm_setup(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K,
     HVAE_REQUIRE(ep.kind != HVAE_EPI_BIAS_GELU_DROP || ep.pre_out, "hvae_gemm_f32: no pre_out");
     HVAE_REQUIRE(ep.kind != HVAE_EPI_GELU_DROP_BWD || ep.pre_in, "hvae_gemm_f32: no pre_in");
   }
-  FastPlan f;
-  if (fp) f = fast_plan(trans_a, trans_b, M, N, K, A, lda, B, ldb, pair_w);
-  int splits = f.bm ? f.splits : gemm_splits(M, N, K);
-  if (splits > 1) {
-    const int64_t fit = ws ? (int64_t)(ws_bytes / ((size_t)(M * N + M) * sizeof(float))) : 0;
-    splits = (int)std::min<int64_t>(splits, fit);
-    if (splits < 2) splits = 1;
-  }
-  int64_t kps = K;
-  if (splits > 1) {
-    kps = cdiv(cdiv(K, splits), GBK) * GBK;
-    splits = (int)cdiv(K, kps);
-  }
-  bt = gemm_tile(M, N, K);
-  if (fp) {
-    f.splits = splits;
-    f.kps = kps;
-    *fp = f;
-  }
-  g.M = M; g.N = N; g.K = K; g.kps = (K == 0) ? 0 : kps;
+  g.M = M; g.N = N; g.K = K;
   g.alpha = alpha; g.A = A; g.lda = lda; g.B = B; g.ldb = ldb; g.beta = beta; g.C = C; g.ldc = ldc;
   g.ep = ep;
-  g.vec_a = (((uintptr_t)A) % 16 == 0) && (lda % 4 == 0);
-  g.vec_b = (((uintptr_t)B) % 16 == 0) && (ldb % 4 == 0);
-  g.gx = (unsigned)cdiv(N, f.bm ? f.bn : bt); g.gy = (unsigned)cdiv(M, f.bm ? f.bm : bt);
-  g.gz = (unsigned)std::max(splits, 1);
-  g.slab = splits > 1 ? (float*)ws : nullptr;
+  return HVAE_OK;
+}
+
+// The plan's share of a checked problem's launch record: k ranges, grid, split-K slab and tickets.
+static int gemm_apply_plan(const hvae_gemm_plan& pl, void* ws, GemmP& g) {
+  g.kps = pl.kps;
+  g.vec_a = pl.vec_a != 0;
+  g.vec_b = pl.vec_b != 0;
+  g.gx = (unsigned)cdiv(g.N, pl.bn); g.gy = (unsigned)cdiv(g.M, pl.bm);
+  g.gz = (unsigned)pl.splits;
+  g.slab = pl.splits > 1 ? (float*)ws : nullptr;
   g.tickets = nullptr;
   if (g.slab) {
     HVAE_REQUIRE((uint64_t)g.gx * g.gy <= (uint64_t)kTicketSlice, "hvae_gemm_f32: too many split tiles");
@@ -1176,22 +1288,19 @@ extern "C" int hvae_gemm_f32(int trans_a, int trans_b, int64_t M, int64_t N, int
     return HVAE_OK;
   }
   GemmP g{};
-  int bt = 32;
-  FastPlan f;
-  if (int rc = gemm_setup(trans_a, trans_b, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, epi, ws, ws_bytes, g,
-                          bt, &f))
-    return rc;
+  if (int rc = gemm_check(trans_a, trans_b, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, epi, g)) return rc;
+  const hvae_gemm_plan pl = plan_one(PlanArgs{trans_a != 0, trans_b != 0, M, N, K, (uintptr_t)A, lda, (uintptr_t)B,
+                                              ldb, ws != nullptr, ws_bytes},
+                                     false);
+  if (int rc = gemm_apply_plan(pl, ws, g)) return rc;
   hipStream_t st = as_stream(stream);
-  if (const int dt = dma_tile(trans_a, trans_b, g)) {
-    const int bm = dt == kTile6432 ? 64 : dt, bn = dt == kTile6432 ? 32 : dt;
-    g.gx = (unsigned)(N / bn);
-    g.gy = (unsigned)(M / bm);
-    dim3 grid(g.gx, g.gy, g.gz);
-    ProbeScope probe("gemm", st);
+  dim3 grid(g.gx, g.gy, g.gz);
+  ProbeScope probe("gemm", st);
+  if (pl.family == 2) {
 #define HVAE_DMA_CALL(TA_, TB_)                                                       \
-  (dt == 64 ? (k_gemm_dma<TA_, TB_, 64, 64><<<grid, 256, 0, st>>>(g))                \
-   : dt == kTile6432 ? (k_gemm_dma<TA_, TB_, 64, 32><<<grid, 256, 0, st>>>(g))       \
-                     : (k_gemm_dma<TA_, TB_, 32, 32><<<grid, 256, 0, st>>>(g)))
+  (pl.bn == 64 ? (k_gemm_dma<TA_, TB_, 64, 64><<<grid, 256, 0, st>>>(g))             \
+   : pl.bm == 64 ? (k_gemm_dma<TA_, TB_, 64, 32><<<grid, 256, 0, st>>>(g))           \
+                 : (k_gemm_dma<TA_, TB_, 32, 32><<<grid, 256, 0, st>>>(g)))
     if (!trans_a && !trans_b) HVAE_DMA_CALL(false, false);
     else if (!trans_a && trans_b) HVAE_DMA_CALL(false, true);
     else if (trans_a && !trans_b) HVAE_DMA_CALL(true, false);
@@ -1200,12 +1309,10 @@ extern "C" int hvae_gemm_f32(int trans_a, int trans_b, int64_t M, int64_t N, int
     HVAE_LAUNCH_CHECK("k_gemm_dma");
     return HVAE_OK;
   }
-  dim3 grid(g.gx, g.gy, g.gz);
-  ProbeScope probe("gemm", st);
-  if (f.bm) {  // trans_a && !trans_b (or, under HVAE_GEMM_FAST_SHORT, !trans_a)
+  if (pl.family == 1) {  // trans_a && !trans_b (or, under HVAE_GEMM_FAST_SHORT, !trans_a)
 #define HVAE_FAST_CALL(TA_, TB_)                                                  \
-  (f.bm == 64 ? (k_gemm_fast<TA_, TB_, 64, 64><<<grid, 256, 0, st>>>(g))        \
-              : (k_gemm_fast<TA_, TB_, 32, 32><<<grid, 256, 0, st>>>(g)))
+  (pl.bm == 64 ? (k_gemm_fast<TA_, TB_, 64, 64><<<grid, 256, 0, st>>>(g))       \
+               : (k_gemm_fast<TA_, TB_, 32, 32><<<grid, 256, 0, st>>>(g)))
     if (trans_a) HVAE_FAST_CALL(true, false);
 #ifdef HVAE_AB
     else if (trans_b) HVAE_FAST_CALL(false, true);
@@ -1215,7 +1322,7 @@ extern "C" int hvae_gemm_f32(int trans_a, int trans_b, int64_t M, int64_t N, int
     HVAE_LAUNCH_CHECK("k_gemm_fast");
     return HVAE_OK;
   }
-  const int nstc = nst_class(trans_a, trans_b, g.kps);
+  const int bt = pl.bm, nstc = pl.nst;
 #define HVAE_GEMM_CALL(TA_, TB_)                                                                  \
   (bt == 64 ? (nstc == kRegStages ? (k_gemm_f32<TA_, TB_, 64, 64, kRegStages><<<grid, 256, 0, st>>>(g))  \
                : nstc == 1 ? (k_gemm_f32<TA_, TB_, 64, 64, 1><<<grid, 256, 0, st>>>(g))                   \
@@ -1239,70 +1346,48 @@ static int gemm_desc(const hvae_gemm_desc* d, void* stream) {
 
 extern "C" int hvae_gemm_f32_pair(const hvae_gemm_desc* w, const hvae_gemm_desc* x, void* stream) {
   HVAE_REQUIRE(w && x, "hvae_gemm_f32_pair: null descriptor");
-  // one launch for the (A^T B, A B) pair of a layer's backward; any other pairing runs as two launches
-  const bool shared_ws = w->ws && w->ws == x->ws && gemm_splits(w->M, w->N, w->K) > 1 &&
-                         gemm_splits(x->M, x->N, x->K) > 1;  // both split-K into one slab: two launches
-  const bool fused = w->trans_a && !w->trans_b && !x->trans_a && !x->trans_b && w->M > 0 && w->N > 0 &&
-                     x->M > 0 && x->N > 0 && !shared_ws;
-  if (!fused) {
+  hvae_gemm_plan pl[2];
+  const int kind = plan_pair(*w, *x, pl);
+  if (kind == 0) {
     if (int rc = gemm_desc(w, stream)) return rc;
     return gemm_desc(x, stream);
   }
   GemmP g0{}, g1{};
-  int bt0 = 32, bt1 = 32;
-  FastPlan f0, f1;
-  if (int rc = gemm_setup(1, 0, w->M, w->N, w->K, w->alpha, w->A, w->lda, w->B, w->ldb, w->beta, w->C, w->ldc,
-                          w->epi, w->ws, w->ws_bytes, g0, bt0, &f0, true))
+  if (int rc = gemm_check(1, 0, w->M, w->N, w->K, w->alpha, w->A, w->lda, w->B, w->ldb, w->beta, w->C, w->ldc,
+                          w->epi, g0))
     return rc;
-  if (int rc = gemm_setup(0, 0, x->M, x->N, x->K, x->alpha, x->A, x->lda, x->B, x->ldb, x->beta, x->C, x->ldc,
-                          x->epi, x->ws, x->ws_bytes, g1, bt1, &f1))
+  if (int rc = gemm_check(0, 0, x->M, x->N, x->K, x->alpha, x->A, x->lda, x->B, x->ldb, x->beta, x->C, x->ldc,
+                          x->epi, g1))
     return rc;
+  if (int rc = gemm_apply_plan(pl[0], w->ws, g0)) return rc;
+  if (int rc = gemm_apply_plan(pl[1], x->ws, g1)) return rc;
   hipStream_t st = as_stream(stream);
-  {
-    const int d0 = dma_tile(true, false, g0, true), d1 = dma_tile(false, false, g1, true);
-    if ((d0 != 0) != (d1 != 0) || (d0 && d1 && g0.slab && g1.slab)) {
-      // one half on the LDS-DMA path, the other not: two launches, so that each half runs the kernel its own
-      // hvae_gemm_f32 call would (the pair stays bitwise the two launches)
-      if (int rc = gemm_desc(w, stream)) return rc;
-      return gemm_desc(x, stream);
-    }
-    if (d0 && d1) {  // both on the LDS-DMA path, one launch
-      g0.gx = (unsigned)(g0.N / d0); g0.gy = (unsigned)(g0.M / d0);
-      g1.gx = (unsigned)(g1.N / d1); g1.gy = (unsigned)(g1.M / d1);
-      const unsigned nblk = g0.gx * g0.gy * g0.gz + g1.gx * g1.gy * g1.gz;
-      ProbeScope probe("gemm", st);
-      if (d0 == 64 && d1 == 64) k_gemm_dma_pair<64, 64><<<nblk, 256, 0, st>>>(g0, g1);
-      else if (d0 == 64) k_gemm_dma_pair<64, 32><<<nblk, 256, 0, st>>>(g0, g1);
-      else if (d1 == 64) k_gemm_dma_pair<32, 64><<<nblk, 256, 0, st>>>(g0, g1);
-      else k_gemm_dma_pair<32, 32><<<nblk, 256, 0, st>>>(g0, g1);
-      HVAE_LAUNCH_CHECK("k_gemm_dma_pair");
-      return HVAE_OK;
-    }
+  const unsigned nblk = g0.gx * g0.gy * g0.gz + g1.gx * g1.gy * g1.gz;
+  ProbeScope probe("gemm", st);
+  const int bt0 = pl[0].bm, bt1 = pl[1].bm;  // (square tiles in every fused kernel)
+  if (kind == 1) {  // both on the LDS-DMA path, one launch
+    if (bt0 == 64 && bt1 == 64) k_gemm_dma_pair<64, 64><<<nblk, 256, 0, st>>>(g0, g1);
+    else if (bt0 == 64) k_gemm_dma_pair<64, 32><<<nblk, 256, 0, st>>>(g0, g1);
+    else if (bt1 == 64) k_gemm_dma_pair<32, 64><<<nblk, 256, 0, st>>>(g0, g1);
+    else k_gemm_dma_pair<32, 32><<<nblk, 256, 0, st>>>(g0, g1);
+    HVAE_LAUNCH_CHECK("k_gemm_dma_pair");
+    return HVAE_OK;
   }
-  if (f0.bm || f1.bm) {
-    if (!f0.bm || f1.bm || (g0.slab && g1.slab)) {  // not (fast dW, register-staged dX): two launches
-      if (int rc = gemm_desc(w, stream)) return rc;
-      return gemm_desc(x, stream);
-    }
-    const unsigned nblk = g0.gx * g0.gy * g0.gz + g1.gx * g1.gy * g1.gz;
-    ProbeScope probe("gemm", st);
-    const int c1 = nst_class(false, false, g1.kps);
+  if (kind == 2) {  // fast dW, register-staged dX
+    const int c1 = pl[1].nst;
 #define HVAE_MIXED(F0_, BT1_)                                                                            \
   (c1 == kRegStages ? (k_gemm_mixed_pair<F0_, BT1_, kRegStages><<<nblk, 256, 0, st>>>(g0, g1))           \
    : c1 == 1 ? (k_gemm_mixed_pair<F0_, BT1_, 1><<<nblk, 256, 0, st>>>(g0, g1))                           \
              : (k_gemm_mixed_pair<F0_, BT1_, kRingStages><<<nblk, 256, 0, st>>>(g0, g1)))
-    if (f0.bm == 64 && bt1 == 64) HVAE_MIXED(64, 64);
-    else if (f0.bm == 64) HVAE_MIXED(64, 32);
+    if (bt0 == 64 && bt1 == 64) HVAE_MIXED(64, 64);
+    else if (bt0 == 64) HVAE_MIXED(64, 32);
     else if (bt1 == 64) HVAE_MIXED(32, 64);
     else HVAE_MIXED(32, 32);
 #undef HVAE_MIXED
     HVAE_LAUNCH_CHECK("k_gemm_mixed_pair");
     return HVAE_OK;
   }
-  const unsigned nblk = g0.gx * g0.gy * g0.gz + g1.gx * g1.gy * g1.gz;
-  ProbeScope probe("gemm", st);
-  // (the register-staged pair keeps two classes: long k ranges on the kRegStages instance's one-tile lookahead)
-  const bool q0 = nst_class(true, false, g0.kps) != kRingStages, q1 = nst_class(false, false, g1.kps) != kRingStages;
+  const bool q0 = pl[0].nst != kRingStages, q1 = pl[1].nst != kRingStages;  // (two classes: plan_pair)
 #define HVAE_PAIR(B0_, B1_)                                                                              \
   (q0 ? (q1 ? (k_gemm_f32_pair<B0_, B1_, kRegStages, kRegStages><<<nblk, 256, 0, st>>>(g0, g1))          \
             : (k_gemm_f32_pair<B0_, B1_, kRegStages, kRingStages><<<nblk, 256, 0, st>>>(g0, g1)))        \
@@ -1326,14 +1411,11 @@ extern "C" int hvae_gemm_f32_multi(const hvae_gemm_desc* d, int n, void* stream)
     HVAE_REQUIRE(d[i].trans_a == 1 && d[i].trans_b == 0, "hvae_gemm_f32_multi: weight gradients only (A^T B)");
     if (d[i].M == 0 || d[i].N == 0) continue;
     GemmP g{};
-    int bt = 32;
     // no workspace: one k range per tile
-    if (int rc = gemm_setup(1, 0, d[i].M, d[i].N, d[i].K, d[i].alpha, d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].beta,
-                            d[i].C, d[i].ldc, d[i].epi, nullptr, 0, g, bt))
+    if (int rc = gemm_check(1, 0, d[i].M, d[i].N, d[i].K, d[i].alpha, d[i].A, d[i].lda, d[i].B, d[i].ldb, d[i].beta,
+                            d[i].C, d[i].ldc, d[i].epi, g))
       return rc;
-    g.gx = (unsigned)cdiv(d[i].N, 32);
-    g.gy = (unsigned)cdiv(d[i].M, 32);
-    g.gz = 1;
+    if (int rc = gemm_apply_plan(plan_multi(plan_args(d[i])), nullptr, g)) return rc;
     m.start[m.n] = nblk;
     m.g[m.n++] = g;
     nblk += g.gx * g.gy;

@@ -15,7 +15,7 @@ import torch
 _HERE = Path(__file__).resolve().parent
 LIB_PATH = Path(os.environ.get("HVAE_LIB", _HERE / "libhvae.so"))
 
-ABI_VERSION = 5  # include/hvae.h HVAE_ABI_VERSION
+ABI_VERSION = 6  # include/hvae.h HVAE_ABI_VERSION
 HVAE_OK = 0
 HVAE_F32 = 0
 HVAE_BF16 = 1
@@ -72,6 +72,11 @@ class GemmDesc(C.Structure):
         ("A", vp), ("lda", i64), ("B", vp), ("ldb", i64), ("beta", f32), ("C", vp), ("ldc", i64),
         ("epi", C.POINTER(Epilogue)), ("ws", vp), ("ws_bytes", sz),
     ]
+
+
+class GemmPlan(C.Structure):  # hvae_gemm_plan
+    _fields_ = [("family", cint), ("bm", cint), ("bn", cint), ("splits", cint), ("kps", i64), ("nst", cint),
+                ("long_k", cint), ("vec_a", cint), ("vec_b", cint)]
 
 
 class MlpRows(C.Structure):  # hvae_mlp_rows
@@ -131,6 +136,8 @@ SIGNATURES = {
                              sz, vp]),
     "hvae_gemm_f32_workspace": (sz, [i64, i64, i64]),
     "hvae_gemm_f32_pair": (cint, [P(GemmDesc), P(GemmDesc), vp]),
+    "hvae_gemm_f32_plan": (cint, [cint, cint, i64, i64, i64, vp, i64, vp, i64, cint, sz, P(GemmPlan)]),
+    "hvae_gemm_f32_pair_plan": (cint, [P(GemmDesc), P(GemmDesc), P(GemmPlan), P(cint)]),
     "hvae_colsum": (cint, [vp, i64, i64, i64, f32, vp, vp, sz, vp]),
     "hvae_colsum_workspace": (sz, [i64, i64]),
     "hvae_reparam_kl_fwd": (cint, [vp, vp, i64, i64, i64, cint, vp, u64, vp, vp, vp, vp, vp]),

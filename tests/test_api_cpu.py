@@ -135,7 +135,7 @@ def test_abi_exports_every_declared_symbol():
     from hvae import _lib
     assert set(_lib.SIGNATURES) == set(syms), "ctypes binding out of sync with include/hvae.h"
     L.hvae_version.restype = ctypes.c_int
-    assert L.hvae_version() == _lib.ABI_VERSION == 5
+    assert L.hvae_version() == _lib.ABI_VERSION == 6
 
 
 def test_abi_argument_errors_without_gpu():
@@ -167,6 +167,8 @@ for n in (0, 1, 4096):
     out += [L.hvae_dense_to_csr_workspace(n, 1_000_000), L.hvae_ln_gelu_drop_bwd_workspace(n, 512),
             L.hvae_w1_rowgrad_workspace(n), L.hvae_gemm_f32_workspace(n, 768, 512),
             L.hvae_gemm_f32_workspace(512, n, 768), L.hvae_gemm_f32_workspace(512, 768, n),
+            # (an empty product over a split-K batch: the fast plan's tile count is 0)
+            L.hvae_gemm_f32_workspace(n, 768, 4096), L.hvae_gemm_f32_workspace(768, n, 4096),
             L.hvae_colsum_workspace(n, 512), L.hvae_clip_grad_norm_workspace(n, 0, 512)]
     for dt in (_lib.HVAE_F32, _lib.HVAE_BF16, _lib.HVAE_FP8):
         out += [L.hvae_decoder_workspace(dt, n, 1_000_000, 768), L.hvae_decoder_workspace(dt, 4096, n, 384),

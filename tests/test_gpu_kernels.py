@@ -31,13 +31,10 @@ def _maxrel(a, b):
 # ------------------------------------------------------------------ GEMM ---
 @pytest.mark.parametrize("M,N,K", [(1, 1, 1), (7, 13, 5), (64, 64, 64), (130, 67, 300), (37, 384, 4096),
                                    (384, 384, 4096), (4096, 128, 512),
-                                   # weight-gradient fast path (trans_a, K >= 1024): 32- and 64-square tiles
-                                   (768, 768, 4096), (256, 64, 2048),
-                                   # whole 64-tiles (the LDS-DMA path's 64 x 64 instance)
-                                   (4096, 768, 256),
-                                   # the LDS-DMA path's 64 x 32 tile (no trans_a, 256 64-square tiles, 512 64 x 32
-                                   # ones: the Syn-10M step's heads / dh shapes)
-                                   (4096, 256, 512)])
+                                   # whole-tile shapes, the train step's at B = 4096 among them. Which kernel each runs is
+                                   # not asserted here: tests/gemm_plan_cases.py lists a shape for every instance the
+                                   # planner can choose, and tests/test_gpu_gemm_plans.py checks that it runs there
+                                   (768, 768, 4096), (256, 64, 2048), (4096, 768, 256), (4096, 256, 512)])
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, False), (True, True)])
 def test_gemm_f32(ops, hip_device, M, N, K, ta, tb):
     g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
