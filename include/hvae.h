@@ -591,7 +591,8 @@ int hvae_topk(const float* scores, int64_t R, int64_t N, int64_t ld, const hvae_
  * candidates are rescored in fp32 and ordered (score desc, item desc), as hvae_topk.
  * idx / val [R, K]; flag[r] = 1 marks rows the fused path could not certify (candidate
  * overflow, fewer than K unseen items, K + |seen| > 256): the caller ranks those
- * exactly (hvae_gemm_f32 + hvae_topk). D in {64, 128, 256, 384, 512, 768}, K <= 256. */
+ * exactly (hvae_gemm_f32 + hvae_topk). D in {64, 128, 256, 384, 512, 768, 1024} (at 1024 the
+ * embedding axis is cut in two halves over pairs of waves), K <= 256. */
 size_t hvae_topk_fused_workspace(int64_t R, int64_t N, int64_t D, int64_t K);
 int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, const float* E32,
                     const float* e32_maxnorm, int64_t N, int64_t D, const hvae_csr_batch* exclude,

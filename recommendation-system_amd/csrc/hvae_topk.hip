@@ -23,6 +23,14 @@
 // relative, so a product by up to 2^-7 + 2^-16; fp32 accumulation on both
 // sides). Users whose candidate lists overflow (or that have fewer than K unseen items, or K_u > 256) are flagged
 // and left to the caller's exact path.
+//
+// d = 1024: all of u as B fragments would be D / 4 = 256 VGPRs per lane, so the k axis is cut in two halves. The
+// seed pass runs the halves one after the other (k_topk_seed_split), the LDS scan gives the halves to the two
+// waves of a pair (k_topk_scan_lds, KH = 2). A score is then half 0's MFMA chain + half 1's, one fp32 add more
+// than the single chain. eps_u keeps its formula: its 4 D 2^-24 term bounds the fp32 rounding of a D-term sum
+// in ANY association (every summation tree of D terms has depth <= D - 1, so its error is at most
+// (D - 1) 2^-24 sum |u_k e_k| <= D 2^-24 ||u|| ||e||; the term allows twice that for each of s~ and s), and
+// two chains of D / 2 plus one add are such a tree.
 #include <climits>
 
 #include <cstdlib>
@@ -53,6 +61,12 @@ __device__ __forceinline__ int tk_ord(float f) {
   return i >= 0 ? i : (i ^ 0x7FFFFFFF);
 }
 __device__ __forceinline__ float tk_unord(int i) { return __int_as_float(i >= 0 ? i : (i ^ 0x7FFFFFFF)); }
+
+// eps_u of the header from ||u||^2 and max ||E||
+template <int D>
+__device__ __forceinline__ float tk_eps(float usq, float emax) {
+  return sqrtf(usq) * emax * (0x1p-7f + 0x1p-16f + 4.0f * D * 0x1p-24f) * 1.02f;
+}
 
 struct TkScanArgs {
   const float* U;
@@ -88,25 +102,27 @@ __device__ __forceinline__ int tk_ku(const TkScanArgs& a, int64_t r) {
 
 // One wave's 32 users: u in registers as bf16 MFMA B fragments, in a permuted k order (group g of 64 k's,
 // step j, lane half h -> k = 64 g + 32 h + 8 j .. + 7, the same order for E's A fragments, so a lane reads
-// 64 contiguous bytes of an E row per group), and S~^T tiles of 32 items.
-template <int D>
+// 64 contiguous bytes of an E row per group), and S~^T tiles of 32 items. With DK < D the scorer holds the DK
+// k's from K0 on only: score() is then that part of the sum and usq that part of ||u||^2 (eps is unused).
+template <int D, int DK = D, int K0 = 0>
 struct TkScorer {
-  static constexpr int NG = D / 64;
+  static constexpr int NG = DK / 64;
+  static_assert(DK % 64 == 0 && K0 % 64 == 0 && K0 + DK <= D, "TkScorer k range");
   uint4 uf[NG][4];
-  float eps;
+  float eps, usq;
   int h, col;
 
   __device__ __forceinline__ void load(const TkScanArgs& a, int64_t user, bool live, int lane) {
     h = lane >> 5;
     col = lane & 31;
-    float usq = 0.f;
+    usq = 0.f;
 #pragma unroll
     for (int g = 0; g < NG; ++g)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
         if (live) {
-          const float* p = a.U + user * a.ldu + 64 * g + 32 * h + 8 * j;
+          const float* p = a.U + user * a.ldu + K0 + 64 * g + 32 * h + 8 * j;
           x = *reinterpret_cast<const float4*>(p);
           y = *reinterpret_cast<const float4*>(p + 4);
         }
@@ -117,7 +133,7 @@ struct TkScorer {
         __builtin_amdgcn_sched_barrier(0);
       }
     usq += __shfl_xor(usq, 32, 64);
-    eps = sqrtf(usq) * (*a.e_maxnorm) * (0x1p-7f + 0x1p-16f + 4.0f * D * 0x1p-24f) * 1.02f;
+    eps = tk_eps<D>(usq, *a.e_maxnorm);
   }
 
   // S~^T of tile t: lane (col = user, h) holds items 32 t + (r & 3) + 8 (r >> 2) + 4 h; past N: -inf
@@ -126,7 +142,7 @@ struct TkScorer {
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] = 0.f;
     const int64_t row = min(t * 32 + col, a.N - 1);  // rows past N: clamped, masked below
-    const unsigned char* er = reinterpret_cast<const unsigned char*>(a.E) + row * (int64_t)(D * 2) + 64 * h;
+    const unsigned char* er = reinterpret_cast<const unsigned char*>(a.E) + row * (int64_t)(D * 2) + 2 * K0 + 64 * h;
     uint4 ea[2][4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) ea[0][j] = *reinterpret_cast<const uint4*>(er + 16 * j);
@@ -168,6 +184,38 @@ __global__ void __launch_bounds__(256) k_topk_seed(TkScanArgs a, int64_t stride,
       for (int r = 0; r < 16; ++r) a.seed[user * kTkSeed + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * sc.h] = s[r];
     }
   }
+}
+
+// The seed pass at d = 1024: the two D-halves one after the other, each over all of the wave's sample tiles.
+// Half 0 stores its partial scores to seed[], half 1 adds its own to them (half 0 + half 1, the scan's order):
+// the same lane wrote the address it reads back, so nothing has to be synchronised.
+template <int D, int K0>
+__device__ __forceinline__ float tk_seed_half(const TkScanArgs& a, int64_t user, bool live, int lane, int w,
+                                              int64_t stride, int nsample) {
+  TkScorer<D, D / 2, K0> sc;
+  sc.load(a, user, live, lane);
+  for (int j = w; j < nsample; j += 4) {
+    const f32x16_t s = sc.score(a, j * stride);
+    if (live) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float* p = a.seed + user * kTkSeed + 32 * j + (r & 3) + 8 * (r >> 2) + 4 * sc.h;
+        *p = K0 == 0 ? s[r] : *p + s[r];
+      }
+    }
+  }
+  return sc.usq;
+}
+
+template <int D>
+__global__ void __launch_bounds__(256) k_topk_seed_split(TkScanArgs a, int64_t stride, int nsample) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t user = (int64_t)blockIdx.x * 32 + (lane & 31);
+  const bool live = user < a.R;
+  float usq = tk_seed_half<D, 0>(a, user, live, lane, w, stride, nsample);
+  usq += tk_seed_half<D, D / 2>(a, user, live, lane, w, stride, nsample);
+  if (live && w == 0 && lane < 32) a.g_eps[user] = tk_eps<D>(usq, *a.e_maxnorm);
 }
 
 // per user: t = (K_u-th largest sample s~) - eps_u, or the lowest bound when the sample holds fewer than K_u items
@@ -295,13 +343,24 @@ __global__ void __launch_bounds__(256) k_topk_scan(TkScanArgs a) {
 // one barrier per tile) and the 32x32x16 A operands are ds_read_b128 row reads of it. Per-user heaps of up to
 // tkl_heap - 1 tile maxima (a user with K_u beyond it keeps the seed / other waves' bound, which is still valid).
 // ring slots and heap capacity per D (LDS: slots x the tile + 4 waves x 32 users x the heap): d = 768 keeps two
-// slots (the next tile's DMA overlaps the current tile's MFMAs) so that K_u up to 64 keeps its heap
+// slots (the next tile's DMA overlaps the current tile's MFMAs) so that K_u up to 64 keeps its heap.
+// d = 1024 (KH = 2): the 4 waves are 2 groups of 32 users x 2 D-halves, so a block takes 64 users. A wave holds
+// the B fragments of its 512 k's (128 VGPRs) and runs its half of the chain over the tile; the odd wave of a pair
+// hands its partial S~^T to the even wave through LDS (4 KiB per group, a second barrier per tile), which adds it
+// (half 0 + half 1) and selects, so both of its lane halves see the same summed scores. LDS: 2 slots x 64 KiB
+// + 8 KiB exchange + 2 x 32 heaps of 63 floats (16 KiB set aside) = 152 KiB.
+constexpr int tkl_kh(int64_t D) { return D >= 1024 ? 2 : 1; }          // D-halves (waves per user group)
+constexpr int tkl_block_users(int64_t D) { return 128 / tkl_kh(D); }  // users per block
 template <int D>
 constexpr int tkl_ns() { return D >= 768 ? 2 : 3; }
 template <int D>
 constexpr int tkl_heap() { return D >= 768 ? 64 : 128; }
 template <int D>
-constexpr int tkl_lds_bytes() { return tkl_ns<D>() * ((D / 128) * 8192) + 4 * 32 * tkl_heap<D>() * 4; }
+constexpr int tkl_xchg_bytes() { return tkl_kh(D) == 2 ? (4 / tkl_kh(D)) * 4096 : 0; }
+template <int D>
+constexpr int tkl_lds_bytes() {
+  return tkl_ns<D>() * ((D / 128) * 8192) + tkl_xchg_bytes<D>() + tkl_block_users(D) * tkl_heap<D>() * 4;
+}
 
 __device__ __forceinline__ uint32_t tk_lds_addr(const void* p) {
   return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
@@ -314,31 +373,36 @@ __device__ __forceinline__ void tk_wait_vmcnt() {
 
 template <int D>
 __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
-  constexpr int NSEG = D / 128, TB = NSEG * 8192, PW = NSEG * 8 / 4, NS = tkl_ns<D>(), KS = D / 16;
+  constexpr int NSEG = D / 128, TB = NSEG * 8192, PW = NSEG * 8 / 4, NS = tkl_ns<D>();
+  constexpr int KH = tkl_kh(D), KS = D / 16 / KH;  // a wave's k-steps: its D-half with KH = 2
   constexpr int HC = tkl_heap<D>() - 1;  // heap capacity = stride: odd, so the 32 users' slots fall on 32 banks
   static_assert(D % 128 == 0 && tkl_lds_bytes<D>() <= 160 * 1024, "k_topk_scan_lds shape");
+  static_assert(KH == 1 || KS / 2 == PW, "the D-split chain issues one DMA piece every second k-step");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  float* heaps = reinterpret_cast<float*>(lds + NS * TB);
+  float* heaps = reinterpret_cast<float*>(lds + NS * TB + tkl_xchg_bytes<D>());
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, col = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ug = w / KH, kh = w % KH;  // the wave's user group and D-half (KH = 1: ug = w, kh = 0)
   const int split = blockIdx.x % a.splits;
-  const int64_t user = (int64_t)(blockIdx.x / a.splits) * 128 + 32 * w + col;
+  const int64_t user = (int64_t)(blockIdx.x / a.splits) * tkl_block_users(D) + 32 * ug + col;
   const bool live = user < a.R;
+  const bool sel_live = live && kh == 0;  // the wave that selects for the group
   const int64_t ntiles = (a.N + 31) / 32;
   const int64_t t0 = (int64_t)split * a.tiles_per_split;
   const int64_t t1 = min(ntiles, t0 + a.tiles_per_split);
   const int64_t nt = t1 > t0 ? t1 - t0 : 0;
   const float emax = *a.e_maxnorm;  // before any LDS-DMA is in flight
 
-  // u as the B operand: lane holds U[user][16 ks + 8 h .. + 7]
+  // u as the B operand: lane holds U[user][16 (KS kh + ks) + 8 h .. + 7]
+  const float* up = a.U + user * a.ldu + 16 * KS * kh + 8 * h;
   uint4 uf[KS];
   float usq = 0.f;
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
     float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
     if (live) {
-      x = *reinterpret_cast<const float4*>(a.U + user * a.ldu + 16 * ks + 8 * h);
-      y = *reinterpret_cast<const float4*>(a.U + user * a.ldu + 16 * ks + 8 * h + 4);
+      x = *reinterpret_cast<const float4*>(up + 16 * ks);
+      y = *reinterpret_cast<const float4*>(up + 16 * ks + 4);
     }
     usq += (x.x * x.x + x.y * x.y) + (x.z * x.z + x.w * x.w) + (y.x * y.x + y.y * y.y) + (y.z * y.z + y.w * y.w);
     uf[ks] = make_uint4(tk_pack_bf16x2(x.x, x.y), tk_pack_bf16x2(x.z, x.w), tk_pack_bf16x2(y.x, y.y),
@@ -346,8 +410,18 @@ __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
     __builtin_amdgcn_sched_barrier(0);  // a few k-steps' loads in flight, not all (register peak)
   }
   usq += __shfl_xor(usq, 32, 64);
-  const float eps = sqrtf(usq) * emax * (0x1p-7f + 0x1p-16f + 4.0f * D * 0x1p-24f) * 1.02f;
-  const int ku = live ? tk_ku(a, user) : 0;
+  if constexpr (KH == 2) {
+    // ||u||^2 = half 0's part + half 1's, handed over through the pair's exchange area (free until the first
+    // tile's barrier); only the selecting wave uses eps
+    float* xu = reinterpret_cast<float*>(lds + NS * TB) + ug * 1024 + lane;
+    if (kh == 1) *xu = usq;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (kh == 0) usq += *xu;
+  }
+  const float eps = tk_eps<D>(usq, emax);
+  const int ku = sel_live ? tk_ku(a, user) : 0;
 
   // LDS-DMA (the decoder's version-2 image: 8-row x 32-column subtiles, 2-bit chunk XOR)
   int vlane[2];
@@ -389,7 +463,10 @@ __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
   const int laneA0 = ((col >> 3) << 11) + ((col & 7) << 6) + (((0 + h) ^ ((col >> 2) & 3)) << 4);
   const int laneA1 = ((col >> 3) << 11) + ((col & 7) << 6) + (((2 + h) ^ ((col >> 2) & 3)) << 4);
 
-  TkSelect sel(a, heaps + (w * 32 + col) * HC, HC, user, live, h, eps, ku, split * 2);
+  // KH = 2: the odd wave of a pair builds the same (unused) selector on the pair's heap; its writes of -inf land
+  // before the first tile's barrier, and it neither consumes nor counts
+  TkSelect sel(a, heaps + (ug * 32 + col) * HC, HC, user, sel_live, h, eps, ku, split * 2);
+  float4* xchg = reinterpret_cast<float4*>(lds + NS * TB) + ug * 256 + lane;  // KH = 2: [4][64 lanes] per group
   if (nt > 0) {
     issue_pieces(tile_soff(t0), 0, 0, PW, true);
     if (NS == 3) issue_pieces(tile_soff(min(t0 + 1, t1 - 1)), 1, 0, PW, true);
@@ -403,8 +480,8 @@ __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
     else tk_wait_vmcnt<0>();
     barrier();  // every wave's pieces of t; every wave is done with the slot the next DMA reuses
     const uint32_t soff_dma = tile_soff(min(t + NS - 1, t1 - 1));
-    const unsigned char* b0 = lds + cur * TB + laneA0;
-    const unsigned char* b1 = lds + cur * TB + laneA1;
+    const unsigned char* b0 = lds + cur * TB + kh * (TB / KH) + laneA0;  // the wave's D-half of the tile
+    const unsigned char* b1 = lds + cur * TB + kh * (TB / KH) + laneA1;
     auto rdA = [&](int ks) {
       const int grp = ks >> 1;
       return __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(((ks & 1) ? b1 : b0) + ((grp >> 2) << 13) +
@@ -425,15 +502,34 @@ __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (KS / 2 < PW) issue_pieces(soff_dma, s_dma, KS / 2, PW, false);
+    if constexpr (KH == 2) {
+      // half 1's partial sums go to the pair's even wave: s = half 0 + half 1, every element added once in
+      // that order. The even wave has read the previous tile's exchange before the barrier above.
+      if (kh == 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xchg[64 * q] = make_float4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+      }
+      barrier();
+      if (kh == 0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float4 p = xchg[64 * q];
+          s[4 * q] += p.x;
+          s[4 * q + 1] += p.y;
+          s[4 * q + 2] += p.z;
+          s[4 * q + 3] += p.w;
+        }
+      }
+    }
     if (t * 32 + 32 > a.N) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= a.N) s[r] = -INFINITY;
     }
-    sel.consume(a, s, t, j);
+    if (kh == 0) sel.consume(a, s, t, j);
   }
   tk_wait_vmcnt<0>();  // the LDS-DMA lands before the block's LDS is released
-  if (live) a.cand_cnt[user * a.nseg + split * 2 + h] = sel.cnt;
+  if (sel_live) a.cand_cnt[user * a.nseg + split * 2 + h] = sel.cnt;
 }
 
 // (score desc, item desc): a before b
@@ -587,11 +683,17 @@ static int tk_wave_users() {  // HVAE_TOPK_WAVE_USERS=0 selects the tile-split m
   return (v && *v) ? (atoi(v) != 0) : 1;
 }
 
-// a split's bf16 slice of E must stay below 2^31 bytes (the LDS scan's buffer resource extent is 32-bit)
+// a split's bf16 slice of E must stay below 2^31 bytes (the LDS scan's buffer resource extent is 32-bit): with
+// cdiv(bytes, 2^30) splits a slice is at most 2^30 bytes + one tile (64 KiB at d = 1024's 2048 B per row)
 constexpr int64_t kTkSplitBytes = (int64_t)1 << 30;
 
-static int tk_splits(int64_t R, int64_t N, int64_t D, int wave_users) {
-  const int64_t groups = std::max<int64_t>(1, cdiv(R, wave_users ? 128 : 32));  // R = 0: a workspace query
+// users per scan block; the workspace's nseg, tk_splits and the launch's block count all go by it
+static int tk_block_users(int64_t D, int lds_scan, int wave_users) {
+  return lds_scan ? tkl_block_users(D) : wave_users ? 128 : 32;
+}
+
+static int tk_splits(int64_t R, int64_t N, int64_t D, int wave_users, int block_users) {
+  const int64_t groups = std::max<int64_t>(1, cdiv(R, block_users));  // R = 0: a workspace query
   const int64_t tiles = cdiv(N, 32);
   int64_t s = std::max<int64_t>(1, cdiv(256, groups));  // ~256 blocks (one per CU: 128 KiB of heaps each)
   s = std::min<int64_t>(s, std::max<int64_t>(1, tiles / (wave_users ? 4 : 16)));  // >= 4 tiles per wave
@@ -605,8 +707,9 @@ static int tk_splits(int64_t R, int64_t N, int64_t D, int wave_users) {
 using namespace hvae;
 
 extern "C" size_t hvae_topk_fused_workspace(int64_t R, int64_t N, int64_t D, int64_t K) {
-  const int wu = tk_lds_scan(D) ? 1 : tk_wave_users();
-  const int s = tk_splits(R, N, D, wu);
+  const int lds_scan = tk_lds_scan(D);
+  const int wu = lds_scan ? 1 : tk_wave_users();
+  const int s = tk_splits(R, N, D, wu, tk_block_users(D, lds_scan, wu));
   const size_t nseg = (size_t)s * (wu ? 2 : 8);
   return 256 + (size_t)R * 8 + (size_t)R * nseg * 4 + (size_t)R * nseg * kTkSegCap * 4 + (size_t)R * kTkSeed * 4;
 }
@@ -624,8 +727,8 @@ extern "C" int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, 
                                int64_t R, int64_t K, int32_t* idx, float* val, int32_t* flag, void* ws,
                                size_t ws_bytes, void* stream) {
   HVAE_REQUIRE(R >= 0 && ldu >= D && K > 0 && K <= kTkHeap && K <= N && N < INT32_MAX, "hvae_topk_fused: bad args");
-  HVAE_REQUIRE(D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768,
-               "hvae_topk_fused: D must be 64, 128, 256, 384, 512 or 768");
+  HVAE_REQUIRE(D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024,
+               "hvae_topk_fused: D must be 64, 128, 256, 384, 512, 768 or 1024");
   if (R == 0) return HVAE_OK;  // an empty batch: its (empty) output tensors may have null data pointers
   HVAE_REQUIRE(U && E_bf16 && E32 && e32_maxnorm && idx && flag, "hvae_topk_fused: null pointer");
   HVAE_REQUIRE(ws && ws_bytes >= hvae_topk_fused_workspace(R, N, D, K), "hvae_topk_fused: workspace too small");
@@ -633,8 +736,12 @@ extern "C" int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, 
     HVAE_REQUIRE(exclude->row_ptr && exclude->col_idx && exclude->nb == R, "hvae_topk_fused: bad exclude");
   hipStream_t st = as_stream(stream);
   const bool lds_scan = tk_lds_scan(D);
+  // d = 1024 has the D-split LDS scan only: the global-load scan (A/B: HVAE_TOPK_LDS=0) would keep all of u in
+  // registers and spill, so it is not instantiated
+  if (D == 1024 && !lds_scan) HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_topk_fused: D = 1024 has no global-load scan");
   const int wu = lds_scan ? 1 : tk_wave_users();
-  const int splits = tk_splits(R, N, D, wu);
+  const int block_users = tk_block_users(D, lds_scan, wu);
+  const int splits = tk_splits(R, N, D, wu, block_users);
   const int nseg = splits * (wu ? 2 : 8);
   HVAE_REQUIRE(!lds_scan || cdiv(cdiv(N, 32), splits) * 32 * D * 2 < ((int64_t)1 << 31),
                "hvae_topk_fused: a split of E exceeds 2^31 bytes");
@@ -654,7 +761,7 @@ extern "C" int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, 
   const int nsample = (int)std::min<int64_t>(ntiles, kTkSeedTiles);
   const int64_t stride = std::max<int64_t>(1, ntiles / nsample);
   const unsigned groups = (unsigned)cdiv(R, 32);  // the seed pass: one block per 32 users
-  const unsigned blocks = (unsigned)(cdiv(R, wu ? 128 : 32) * splits);
+  const unsigned blocks = (unsigned)(cdiv(R, block_users) * splits);
   const size_t lds = (size_t)4 * 32 * (kTkHeap + kTkHeapPad) * 4;
 #define TK_SCAN_LDS(DD)                                                                                 \
   {                                                                                                       \
@@ -681,6 +788,14 @@ extern "C" int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, 
     break;
     TK_CASE(64) TK_CASE(128) TK_CASE(256) TK_CASE(384) TK_CASE(512) TK_CASE(768)
 #undef TK_CASE
+    case 1024:  // the D-split seed and LDS scan
+      k_topk_seed_split<1024><<<groups, 256, 0, st>>>(sa, stride, nsample);
+      HVAE_LAUNCH_CHECK("k_topk_seed_split");
+      k_topk_seed_select<<<(unsigned)R, 256, 0, st>>>(sa, nsample);
+      HVAE_LAUNCH_CHECK("k_topk_seed_select");
+      TK_SCAN_LDS(1024)
+      HVAE_LAUNCH_CHECK("k_topk_scan");
+      break;
 #undef TK_SCAN_LDS
   }
   TkSelArgs la{U, ldu, E32, R, N, D, exclude ? exclude->row_ptr : nullptr, exclude ? exclude->col_idx : nullptr,
@@ -692,7 +807,8 @@ extern "C" int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, 
     case 256: k_topk_select<4><<<(unsigned)R, 256, 0, st>>>(la); break;
     case 384: k_topk_select<6><<<(unsigned)R, 256, 0, st>>>(la); break;
     case 512: k_topk_select<8><<<(unsigned)R, 256, 0, st>>>(la); break;
-    default: k_topk_select<12><<<(unsigned)R, 256, 0, st>>>(la); break;
+    case 768: k_topk_select<12><<<(unsigned)R, 256, 0, st>>>(la); break;
+    default: k_topk_select<16><<<(unsigned)R, 256, 0, st>>>(la); break;
   }
   HVAE_LAUNCH_CHECK("k_topk_select");
   return HVAE_OK;

@@ -1,7 +1,8 @@
 """Eval / serving throughput on MI355X (users/s), beside the reference's measured 374 users/s (CPU,
 All_Beauty, 99-negative protocol of src/ml/evaluate.py:149-215).
 
-    python scripts/bench_eval.py [--workload all_beauty|syn1m|syn10m] [--batch 1024] [--k 20] [--reps 5]
+    python scripts/bench_eval.py [--workload all_beauty|syn1m|syn1m_d1024|syn10m] [--batch 1024] [--k 20]
+                                 [--reps 5]
 
 Lines (JSON, one per measurement):
   * topk_fused     full-ranking top-k of a batch of users (seen items excluded): encoder -> u -> hvae_topk_fused
@@ -28,6 +29,8 @@ WORKLOADS = {
     "all_beauty": dict(users=22363, items=12101, d=384, lam=3.0),
     "syn1m": dict(users=200000, items=100000, d=384, lam=15.0),
     "syn10m": dict(users=200000, items=1000000, d=768, lam=15.0),
+    # the widest embedding: the D-split fused top-K against the score matrix (1.6 GB at --batch 4096)
+    "syn1m_d1024": dict(users=200000, items=100000, d=1024, lam=15.0),
 }
 
 
@@ -82,7 +85,9 @@ def main():
         finally:
             os.environ.pop("HVAE_TOPK_LDS")
 
-    arms = [("topk_fused", run_fused), ("topk_fused_global_scan", run_fused_global)] + \
+    # d = 1024 has no global-load scan (hvae_topk.hip: it would spill)
+    arms = [("topk_fused", run_fused)] + \
+        ([] if w["d"] == 1024 else [("topk_fused_global_scan", run_fused_global)]) + \
         ([] if args.skip_matrix else [("topk_matrix", run_matrix)])
     if args.probes:
         arms = [a for a in arms if a[0] in args.probes]
