@@ -650,6 +650,59 @@ int hvae_knn_scores(const hvae_csr_batch* x, const int64_t* col_ptr, const int32
                     const double* inv_norm, int64_t n_users, const double* T, size_t t_bytes, int zero_diag,
                     float* out, int64_t ld, void* stream);
 
+/* -------------------------------------------------------- LightGCN (K18) -- */
+/* The LightGCN baseline (LightGCNModel / LightGCNRecommender, src/ml/baseline.py:239-385) over the bipartite graph
+ * of the interaction matrix M [n_users, n_items]. The nodes are one table [n_users + n_items, d], users first (the
+ * reference's torch.cat([user_emb, item_emb])). The graph is M's CSR (row_ptr / col_idx) and CSC (col_ptr /
+ * row_idx), both de-duplicated and free of explicit zeros: only the structure counts (M.nonzero(), :297), a summed
+ * value of 2.0 is one edge. Everything is fp32 without floating-point atomics, every sum in one fixed order that
+ * depends on the graph (or the batch plan) only: two runs are bitwise equal. d is 64 or 128; n_users + n_items
+ * < 2^31.
+ *
+ * hvae_lgcn_norm: scale[r] = deg(r)^-1/2 in double, 0 for an isolated node (:306-310); deg is the CSR row length
+ * of a user and the CSC column length of an item. scale [n_users + n_items]. The weight of edge (u, i) is
+ * (float)(scale[u] * scale[n_users + i]), formed where it is used (the reference's FloatTensor(norm_vals), :313-316);
+ * no per-edge array exists. */
+int hvae_lgcn_norm(const int64_t* row_ptr, int64_t n_users, const int64_t* col_ptr, int64_t n_items, double* scale,
+                   void* stream);
+typedef struct hvae_lgcn_graph {
+  const int64_t* row_ptr; /* [n_users + 1]                                  */
+  const int32_t* col_idx; /* item ids, every one in [0, n_items)            */
+  const int64_t* col_ptr; /* [n_items + 1]                                  */
+  const int32_t* row_idx; /* user ids, every one in [0, n_users)            */
+  const double* scale;    /* hvae_lgcn_norm's output                        */
+  int64_t n_users, n_items;
+} hvae_lgcn_graph;
+/* out[r] = alpha * (add[r] + sum_{j in N(r)} w_rj x[j]) for every node r in one launch; x, add, out are
+ * [n_users + n_items, d] tables. add may be NULL (taken as 0) and may alias out; out may not alias x. An isolated
+ * node gets exactly alpha * add[r]. The adjacency A is symmetric, so the layer mean of LightGCNModel.forward
+ * (:256-266) and its backward are the same Horner chain of n_layers launches, each with add = the chain's input
+ * and alpha = 1 except 1 / (n_layers + 1) on the last:
+ *   n_layers = 3:  F = 1/4 (E + A(E + A(E + A E))),   dE = 1/4 (g + A(g + A(g + A g))).
+ * A wave owns a row (one lane per column at d = 64, two at 128) and walks its neighbours in storage order, 64
+ * indices at a time, over four accumulators merged (a0 + a1) + (a2 + a3); a row of more than 256 neighbours is
+ * cut into four contiguous quarters over the waves of its block, merged ((q0 + q1) + q2) + q3. A neighbour index
+ * outside its range yields NaN in that row, never a read out of bounds. */
+int hvae_lgcn_propagate(const hvae_lgcn_graph* g, int64_t d, const float* x, const float* add, float* out,
+                        float alpha, void* stream);
+/* The BPR loss of one batch of nb <= HVAE_LGCN_MAX_BATCH triples (users[b], pos[b], neg[b]) (int32, device) over the
+ * propagated table F (LightGCNRecommender.fit, :354-367):
+ *   loss = -mean_b logsigmoid(F_u . F_p - F_u . F_n) + reg * (|F[users]|^2 + |F[pos]|^2 + |F[neg]|^2) / nb
+ * written to *loss_out (fp32, nullable) and added to *loss_accum (double, nullable), and its gradient with respect
+ * to F into g [n_users + n_items, d], which is cleared first: zero off the batch's rows. A node that occurs several
+ * times (a repeated user, an item that is a positive and a negative) has its contributions summed by one wave in
+ * the order of the plan: slots [3 nb] holds the occurrence ids role * nb + b (role 0 user, 1 positive, 2 negative)
+ * grouped by node, ascending within a node, and seg_off [n_seg + 1] the groups' bounds (n_seg = the batch's
+ * distinct nodes). The plan is the caller's, built from the indices the host already has (a stable sort by node
+ * id); a plan that contradicts the indices yields NaN rows, an index outside its range a NaN loss. ws:
+ * hvae_lgcn_bpr_workspace(nb) bytes, 8-byte aligned. */
+#define HVAE_LGCN_MAX_BATCH 1024
+size_t hvae_lgcn_bpr_workspace(int64_t nb);
+int hvae_lgcn_bpr(const float* F, int64_t n_users, int64_t n_items, int64_t d, const int32_t* users,
+                  const int32_t* pos, const int32_t* neg, int64_t nb, const int32_t* slots, const int32_t* seg_off,
+                  int64_t n_seg, double reg, float* g, float* loss_out, double* loss_accum, void* ws,
+                  size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and
  * released by hvae_host_csr_free. */

@@ -109,8 +109,15 @@ class AdamPend(C.Structure):  # hvae_adam_pend: a deferred W1t update's record (
     _fields_ = [("slot_of", vp), ("item_of", vp), ("hdr", vp)]
 
 
+class LgcnGraph(C.Structure):  # hvae_lgcn_graph
+    _fields_ = [("row_ptr", vp), ("col_idx", vp), ("col_ptr", vp), ("row_idx", vp), ("scale", vp), ("n_users", i64),
+                ("n_items", i64)]
+
+
+LGCN_MAX_BATCH = 1024  # include/hvae.h HVAE_LGCN_MAX_BATCH
+
 P = C.POINTER
-# name -> (restype, argtypes); mirrors include/hvae.h one to one.
+# name ->(restype, argtypes); mirrors include/hvae.h one to one.
 SIGNATURES = {
     "hvae_version": (cint, []),
     "hvae_last_error": (cint, [C.c_char_p, sz]),
@@ -191,6 +198,10 @@ SIGNATURES = {
     "hvae_knn_user_weights": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, vp]),
     "hvae_knn_score_candidates": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, vp, i64, cint, vp, vp]),
     "hvae_knn_scores": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, cint, vp, i64, vp]),
+    "hvae_lgcn_norm": (cint, [vp, i64, vp, i64, vp, vp]),
+    "hvae_lgcn_propagate": (cint, [P(LgcnGraph), i64, vp, vp, vp, f32, vp]),
+    "hvae_lgcn_bpr_workspace": (sz, [i64]),
+    "hvae_lgcn_bpr": (cint, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, i64, f64, vp, vp, vp, vp, sz, vp]),
     "hvae_cast_bf16": (cint, [vp, vp, i64, vp]),
     "hvae_negatives_legacy": (cint, [vp, vp, vp, i64, vp, i64, vp, vp, i64, C.c_int32, vp, vp]),
     "hvae_read_interactions": (cint, [C.c_char_p, C.c_char_p, i64, i64, C.c_char_p, i64, i64, cint,

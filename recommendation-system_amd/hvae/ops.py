@@ -616,3 +616,139 @@ def knn_scores(x: Csr, m: Csc, inv_norm: torch.Tensor, T: torch.Tensor, zero_dia
                                 ptr(T), T.numel() * T.element_size(), int(bool(zero_diag)), ptr(out),
                                 out.stride(0), stream_of(inv_norm)), "hvae_knn_scores")
     return out
+
+
+# ----------------------------------------------------------------- LightGCN --
+LGCN_DIMS = (64, 128)  # hvae_lgcn_propagate / hvae_lgcn_bpr (include/hvae.h)
+
+
+class LgcnGraph:
+    """The bipartite user-item graph of an interaction matrix as hvae_lgcn_* read it: the device CSR and CSC of the
+    structure (duplicates merged, explicit zeros dropped) and the degree scales deg^-1/2 (fp64, lgcn_norm)."""
+
+    def __init__(self, csr: Csr, csc: Csc):
+        if csr.nb != csc.n_users or csr.n_items != csc.n_items:
+            raise ValueError("LgcnGraph: the CSR and the CSC are of different matrices")
+        if csr.col_idx.numel() != csc.row_idx.numel():
+            raise ValueError("LgcnGraph: the CSR and the CSC hold different numbers of entries")
+        self.csr, self.csc = csr, csc
+        self.n_users, self.n_items = csc.n_users, csc.n_items
+        self.n_nodes = self.n_users + self.n_items
+        self.nnz = int(csr.col_idx.numel())
+        self.device = csr.row_ptr.device
+        self.scale = torch.empty(self.n_nodes, dtype=torch.float64, device=self.device)
+        self.struct = _lib.LgcnGraph(ptr(csr.row_ptr), ptr(csr.col_idx), ptr(csc.col_ptr), ptr(csc.row_idx),
+                                     ptr(self.scale), self.n_users, self.n_items)
+        lgcn_norm(self)
+
+    @property
+    def ref(self):
+        return C.byref(self.struct)
+
+
+def lgcn_graph_from_scipy(mat, device) -> LgcnGraph:
+    """Upload the structure of a scipy.sparse interaction matrix (mat.nonzero(): duplicates are one edge, explicit
+    zeros none) as an LgcnGraph."""
+    m = mat.tocsr().copy()
+    m.sum_duplicates()
+    m.eliminate_zeros()
+    m.sort_indices()
+    return LgcnGraph(csr_from_scipy(m, device), csc_from_scipy(m, device))
+
+
+def lgcn_norm(graph: LgcnGraph) -> torch.Tensor:
+    """graph.scale[r] = deg(r)^-1/2 in double, 0 for an isolated node (hvae_lgcn_norm); returns it."""
+    check(lib().hvae_lgcn_norm(ptr(graph.csr.row_ptr), graph.n_users, ptr(graph.csc.col_ptr), graph.n_items,
+                               ptr(graph.scale), stream_of(graph.scale)), "hvae_lgcn_norm")
+    return graph.scale
+
+
+def _lgcn_table(graph: LgcnGraph, name: str, t: torch.Tensor | None):
+    if t is None:
+        return
+    require_hip(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] != graph.n_nodes or not t.is_contiguous():
+        raise ValueError(f"lgcn: {name} must be a contiguous fp32 [{graph.n_nodes}, d] table, got "
+                         f"{tuple(t.shape)} {t.dtype}")
+    if t.shape[1] not in LGCN_DIMS:
+        raise ValueError(f"lgcn: embedding_dim {t.shape[1]} is not served; served: {LGCN_DIMS[0]} and {LGCN_DIMS[1]}")
+
+
+def lgcn_propagate(graph: LgcnGraph, x: torch.Tensor, add: torch.Tensor | None = None,
+                   out: torch.Tensor | None = None, alpha: float = 1.0) -> torch.Tensor:
+    """out[r] = alpha * (add[r] + sum_{j in N(r)} w_rj x[j]) over every node (hvae_lgcn_propagate); out may not
+    alias x."""
+    _lgcn_table(graph, "x", x)
+    _lgcn_table(graph, "add", add)
+    if out is None:
+        out = torch.empty_like(x)
+    _lgcn_table(graph, "out", out)
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError("lgcn_propagate: out may not alias x")
+    if (add is not None and add.shape != x.shape) or out.shape != x.shape:
+        raise ValueError("lgcn_propagate: x, add and out must have one shape")
+    check(lib().hvae_lgcn_propagate(graph.ref, x.shape[1], ptr(x), ptr(add), ptr(out), float(alpha), stream_of(x)),
+          "hvae_lgcn_propagate")
+    return out
+
+
+def lgcn_chain(graph: LgcnGraph, e: torch.Tensor, n_layers: int, out: torch.Tensor, tmp_a: torch.Tensor,
+               tmp_b: torch.Tensor) -> torch.Tensor:
+    """The mean of e, A e, ..., A^n_layers e as a Horner chain of n_layers launches into out (tmp_a, tmp_b: two
+    tables of e's shape). The adjacency is symmetric, so this is also the backward of itself."""
+    if not 1 <= n_layers <= 8:
+        raise ValueError(f"lgcn: n_layers {n_layers} is not served; served: 1 to 8")
+    x = e
+    for k in range(n_layers):
+        last = k == n_layers - 1
+        dst = out if last else (tmp_a if k % 2 == 0 else tmp_b)
+        lgcn_propagate(graph, x, e, dst, 1.0 / (n_layers + 1) if last else 1.0)
+        x = dst
+    return out
+
+
+def lgcn_bpr_plan(users, pos, neg, n_users: int):
+    """Host plan of one batch for lgcn_bpr: (slots int32 [3 nb], seg_off int32 [n_seg + 1]) -- the occurrence ids
+    role * nb + b (role 0 user, 1 positive, 2 negative) grouped by node and ascending within a node (a stable sort
+    by node id), and the groups' bounds."""
+    import numpy as np
+    node = np.concatenate([np.asarray(users, np.int64), np.asarray(pos, np.int64) + n_users,
+                           np.asarray(neg, np.int64) + n_users])
+    order = np.argsort(node, kind="stable")
+    srt = node[order]
+    starts = np.flatnonzero(np.concatenate([[True], srt[1:] != srt[:-1]]))
+    return order.astype(np.int32), np.concatenate([starts, [len(node)]]).astype(np.int32)
+
+
+def lgcn_bpr(F: torch.Tensor, n_users: int, users: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, reg: float,
+             g: torch.Tensor | None = None, loss_accum: torch.Tensor | None = None, plan=None, n_seg: int | None = None):
+    """(loss fp32 [1], g) of one BPR batch over the propagated table F (hvae_lgcn_bpr): g [n_nodes, d] is cleared
+    and holds the gradient with respect to F; the loss is also added to loss_accum (fp64 [1]) when given. plan:
+    device (slots, seg_off) of lgcn_bpr_plan with n_seg groups; built here from the indices (one device-to-host
+    copy) when not given."""
+    require_hip(F, users, pos, neg, g, loss_accum)
+    n_nodes, d = F.shape
+    if d not in LGCN_DIMS:
+        raise ValueError(f"lgcn: embedding_dim {d} is not served; served: {LGCN_DIMS[0]} and {LGCN_DIMS[1]}")
+    nb = users.numel()
+    if not 1 <= nb <= _lib.LGCN_MAX_BATCH or pos.numel() != nb or neg.numel() != nb:
+        raise ValueError(f"lgcn_bpr: a batch of {nb} triples (served: 1 to {_lib.LGCN_MAX_BATCH}, three equal lengths)")
+    for t in (users, pos, neg):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    assert F.dtype == torch.float32 and F.is_contiguous()
+    if plan is None:
+        s, o = lgcn_bpr_plan(users.cpu().numpy(), pos.cpu().numpy(), neg.cpu().numpy(), n_users)
+        plan, n_seg = (torch.as_tensor(s, device=F.device), torch.as_tensor(o, device=F.device)), len(o) - 1
+    slots, seg_off = plan
+    assert slots.dtype == torch.int32 and seg_off.dtype == torch.int32
+    assert slots.numel() >= 3 * nb and seg_off.numel() >= n_seg + 1
+    if g is None:
+        g = torch.empty_like(F)
+    assert g.shape == F.shape and g.dtype == torch.float32 and g.is_contiguous()
+    assert loss_accum is None or loss_accum.dtype == torch.float64
+    loss = torch.empty(1, dtype=torch.float32, device=F.device)
+    ws = workspace(F.device, lib().hvae_lgcn_bpr_workspace(nb))
+    check(lib().hvae_lgcn_bpr(ptr(F), n_users, n_nodes - n_users, d, ptr(users), ptr(pos), ptr(neg), nb, ptr(slots),
+                              ptr(seg_off), int(n_seg), float(reg), ptr(g), ptr(loss), ptr(loss_accum), ptr(ws),
+                              ws.numel(), stream_of(F)), "hvae_lgcn_bpr")
+    return loss, g
