@@ -54,8 +54,15 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 #ifndef DEC5_G1_AHEAD
 #define DEC5_G1_AHEAD 2  // GEMM1 A operand k-steps in flight
 #endif
+#ifndef DEC5_G2_AHEAD
+#define DEC5_G2_AHEAD 2  // GEMM2 E^T operands (two transposed reads, 4 VGPRs each) in flight ahead of their MFMA
+#endif
+#ifndef DEC5_G1PRIO
+#define DEC5_G1PRIO 0  // A/B: s_setprio 1 over the P32 producer's GEMM1 MFMAs only, 0 again before its softmax tail
+#endif
 #ifndef DEC5_DMA_B
-#define DEC5_DMA_B 6  // of each (ug, dh)'s 12 LDS-DMA pieces per tile, how many the consumer wave issues
+#define DEC5_DMA_B 4  // of each (ug, dh)'s 12 LDS-DMA pieces per tile, how many the consumer wave issues (the producer's
+                      // trimmed loop takes 8: DESIGN.md 4.1a, round 7)
 #endif
 // Timing-ablation builds only (scripts/build_variant5.sh; outputs invalid by construction), a bit mask:
 // 1 no LDS-DMA pieces in the loop (and no vmcnt waits), 2 no per-tile barrier, 4 no exponentials / P out,

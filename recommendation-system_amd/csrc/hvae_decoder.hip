@@ -1671,12 +1671,17 @@ static DecPlan dec_plan(int dtype, int64_t nb, int64_t N, int64_t D) {
   return p;
 }
 
-// workspace: flags [splits * nb] | partials (m, l, O) [splits * nb * (D + 2)] (splits > 1) | O scratch [nb * D]
+// workspace: flags [splits * nb] | partials m, l [2 splits * nb, padded to 16 B] and O [splits * nb * D]
+// (splits > 1) | O scratch [nb * D]. The O partials start 16-B aligned whatever splits * nb is: the finalize
+// picks its 16-B column form by its operands' alignment (fin_v4), and that form fixes the order of the sparse
+// dot product's sum, which has to be hvae_decoder_bwd's for the fused call to equal forward + backward bitwise
 static size_t dec_flag_bytes(int splits, int64_t nb) {
   return (size_t)cdiv((int64_t)splits * nb * sizeof(int), 256) * 256;
 }
+static size_t dec_ml_floats(int splits, int64_t nb) { return (size_t)cdiv((int64_t)2 * splits * nb, 4) * 4; }
 static size_t dec_ws_bytes(int splits, int64_t nb, int64_t D) {
-  return dec_flag_bytes(splits, nb) + (splits > 1 ? (size_t)splits * nb * (D + 2) * sizeof(float) : 0) +
+  return dec_flag_bytes(splits, nb) +
+         (splits > 1 ? (dec_ml_floats(splits, nb) + (size_t)splits * nb * D) * sizeof(float) : 0) +
          (size_t)nb * D * sizeof(float);
 }
 
@@ -1991,7 +1996,7 @@ static int decoder_run(int dtype, const float* U, int64_t ldu, const void* E, co
     o.direct = 0;
     o.m = base;
     o.l = base + (size_t)p.splits * nb;
-    o.O = base + (size_t)2 * p.splits * nb;
+    o.O = base + dec_ml_floats(p.splits, nb);
   }
   int rc;
   {

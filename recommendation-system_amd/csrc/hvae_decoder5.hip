@@ -29,6 +29,7 @@
 // takes 9.4 ms of the 10.1-10.4, while the MFMAs alone take 6.9.
 #include <algorithm>
 #include <array>
+#include <type_traits>
 
 #include "hvae_common.h"
 #include "hvae_dec5_shared.h"
@@ -123,28 +124,46 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
 #else
 #define DEC5_POL ""
 #endif
-  auto issue_piece = [&](uint32_t soff, int slot_i, int i, bool fresh) {
+  // One piece into the slot whose ring base (ring0 + slot bytes) is lb, from the tile at image offset soff. The
+  // piece's own image offset depends on the wave (q) but not on the tile: the compiler hoists it out of the loops
+  // into an SGPR. Product form: M0 and the load's soffset cost one scalar add each, and the second add stands in the
+  // wait state an LDS-DMA load needs after a write of M0. Every form names m0 as clobbered
+  auto dma_piece = [&](uint32_t lb, uint32_t soff, int i, bool fresh) {
     if ((DEC5_ABL & 256) && (i & 1)) return;
-    const uint32_t lb = ring0 + (uint32_t)(slot_i * TB);
     const int p = q * PW + i;
-    const uint32_t so = soff + (uint32_t)(8 * ((p >> 1) & 3) * (D * 2) + 256 * (p >> 3) + 128 * (p & 1));
+    const uint32_t po = (uint32_t)(8 * ((p >> 1) & 3) * (D * 2) + 256 * (p >> 3) + 128 * (p & 1));
     const int vo = ((p >> 1) & 1) ? vlane[1] : vlane[0];
 #if DEC5_GLDS
-    const unsigned char* src = reinterpret_cast<const unsigned char*>(E) + so;  // wave-uniform: an SGPR pair
+    const unsigned char* src = reinterpret_cast<const unsigned char*>(E) + (soff + po);  // wave-uniform: an SGPR pair
     if (fresh)
       asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" DEC5_POL
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(src) : "memory");
+                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(src) : "memory", "m0");
     else
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" DEC5_POL
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(src) : "memory");
-#else
+                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(src) : "memory", "m0");
+#elif DEC5_ROT  // i is not a compile-time constant
     if (fresh)
       asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" DEC5_POL " lds"
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(rsrc), "s"(so) : "memory");
+                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(rsrc), "s"(soff + po) : "memory", "m0");
     else
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" DEC5_POL " lds"
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(rsrc), "s"(so) : "memory");
+                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(rsrc), "s"(soff + po) : "memory", "m0");
+#else
+    uint32_t so;
+    if (fresh)
+      asm volatile("s_nop 4\n\ts_add_u32 m0, %2, %3\n\ts_add_u32 %0, %4, %5\n\t"
+                   "buffer_load_dwordx4 %1, %6, %0 offen" DEC5_POL " lds"
+                   : "=&s"(so) : "v"(vo), "s"(lb), "i"(i * 1024), "s"(soff), "s"(po), "s"(rsrc)
+                   : "memory", "m0", "scc");
+    else
+      asm volatile("s_add_u32 m0, %2, %3\n\ts_add_u32 %0, %4, %5\n\t"
+                   "buffer_load_dwordx4 %1, %6, %0 offen" DEC5_POL " lds"
+                   : "=&s"(so) : "v"(vo), "s"(lb), "i"(i * 1024), "s"(soff), "s"(po), "s"(rsrc)
+                   : "memory", "m0", "scc");
 #endif
+  };
+  auto issue_piece = [&](uint32_t soff, int slot_i, int i, bool fresh) {
+    dma_piece(ring0 + (uint32_t)(slot_i * TB), soff, i, fresh);
   };
   auto tile_soff = [&](int64_t t) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)(t * (int64_t)(kTI * D * 2)));
@@ -160,6 +179,16 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   // lines at a time
   const int rot = __builtin_amdgcn_readfirstlane(ublk);
   auto prot = [&](int i, int n) { return DEC5_ROT ? (i + rot) % n : i; };
+  // The tile loops run on 32-bit scalars: the split's tile count, the image offset of the tile the DMA fetches
+  // (running; the image is below 2 GiB, the buffer resource's rule) and the ring's slot offsets rotating through
+  // three SGPRs. Their last two iterations, which fetch nothing, are peeled off, so the steady-state bodies issue
+  // their pieces unconditionally; only the sweep's last tile, reached in the peeled part, can need the tail mask
+  constexpr uint32_t kTileStep = (uint32_t)(kTI * D * 2);
+  constexpr uint32_t kPPar = 2 * 32 * PST;  // bytes between the two parities of pbuf
+  const int n_tiles = __builtin_amdgcn_readfirstlane(t_beg < t_end ? (int)(t_end - t_beg) : 0);
+  // this split's last tile is the sweep's and partial / its item count (asked where used, not held in registers)
+  auto tail_last = [&] { return t_end == ntiles && (N % kTI) != 0; };
+  auto tail_items = [&] { return (int)(N - (ntiles - 1) * kTI); };
   if ((DEC5_PRIO == 1 && role == 1) || (DEC5_PRIO == 2 && role == 0)) __builtin_amdgcn_s_setprio(1);
 
   if (DEC5_P32 && role == 0) {
@@ -182,7 +211,8 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const float* up = U + ur * ldu + 32 * ks + 8 * g;
-        if (ks > 0) asm volatile("" : "+v"(up) : "v"(uf[uh][ks - 1]));  // one k-step's loads live at a time
+        // one k-step's loads live at a time, its squares summed before the next step's loads
+        if (ks > 0) asm volatile("" : "+v"(up) : "v"(uf[uh][ks - 1]), "v"(usq));
         float4 a = *reinterpret_cast<const float4*>(up);
         float4 b = *reinterpret_cast<const float4*>(up + 4);
         a.x *= keep; a.y *= keep; a.z *= keep; a.w *= keep;
@@ -212,6 +242,7 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
 #pragma unroll
       for (int j = 0; j < AH; ++j) a[j] = rdA(j);
       __builtin_amdgcn_sched_barrier(0);
+      if (DEC5_G1PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const bf16x8 c = a[ks % AH];
@@ -221,19 +252,20 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
         fill(ks);
         __builtin_amdgcn_sched_barrier(0);
       }
+      if (DEC5_G1PRIO) __builtin_amdgcn_s_setprio(0);
     };
     float m[2] = {0.f, 0.f}, mL[2] = {0.f, 0.f}, lsum[2] = {0.f, 0.f};
     f32x4 s_nx[2];
-    auto mask_tail = [&](f32x4 (&s)[2], int64_t t) {
-      if (t == ntiles - 1 && (N % kTI) != 0) {
-        const int lim = (int)(N - t * kTI) - 16 * ih - 4 * gi;
+    auto mask_tail = [&](f32x4 (&s)[2]) {  // the sweep's last tile, when N % 32 != 0: items past N get P = 0
+      const int lim = tail_items() - 16 * ih - 4 * gi;
 #pragma unroll
-        for (int uh = 0; uh < 2; ++uh)
+      for (int uh = 0; uh < 2; ++uh)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) s[uh][r] = r >= lim ? -INFINITY : s[uh][r];
-      }
+        for (int r = 0; r < 4; ++r) s[uh][r] = r >= lim ? -INFINITY : s[uh][r];
     };
-    auto p_out = [&](int par) {  // 8 exponentials (4 items x 2 users), the sums, the packed P row pieces -> LDS
+    // this lane's P piece of parity 0, user half 0; parity 1 is kPPar bytes on, user half 1 16 rows on
+    unsigned char* const pw0 = p_row(0, c16) + 2 * (16 * ih + 8 * (gi & 1) + 4 * (gi >> 1));
+    auto p_out = [&](uint32_t poff) {  // 8 exponentials (4 items x 2 users), the sums, the packed P row pieces -> LDS
 #pragma unroll
       for (int uh = 0; uh < 2; ++uh) {
         float pv[4];
@@ -253,21 +285,24 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
           pv[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s_nx[uh][r], kLog2e, -mL[uh]));
           lsum[uh] += pv[r];
         }
-        *reinterpret_cast<uint2*>(p_row(par, 16 * uh + c16) + 2 * (16 * ih + 8 * (gi & 1) + 4 * (gi >> 1))) =
+        *reinterpret_cast<uint2*>(pw0 + poff + uh * 16 * PST) =
             make_uint2(pack_bf16x2(pv[0], pv[1]), pack_bf16x2(pv[2], pv[3]));
       }
     };
     if (t_beg < t_end) {
+#pragma unroll
       for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg), 0, i, i == 0);
-      if (t_beg + 1 < t_end)
+      if (t_beg + 1 < t_end) {
+#pragma unroll
         for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+      }
       wait_vmcnt<0>();
     }
     barrier();  // [P0] tiles t_beg (and t_beg + 1) landed (consumers' pieces too)
     float mh[2] = {0.f, 0.f};
     if (t_beg < t_end) {
       gemm1(lds, s_nx, [](int) {});
-      mask_tail(s_nx, t_beg);
+      if (n_tiles == 1 && tail_last()) mask_tail(s_nx);
 #pragma unroll
       for (int uh = 0; uh < 2; ++uh) {
         float mx = fmaxf(fmaxf(s_nx[uh][0], s_nx[uh][1]), fmaxf(s_nx[uh][2], s_nx[uh][3]));
@@ -287,27 +322,42 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
       p_out(0);  // P(t_beg) -> parity 0
     }
     barrier();  // [P1]
-    for (int64_t t = t_beg; t < t_end; ++t) {
-      const int li = (int)(t - t_beg);
-      const int nxt = (li + 1) % NS, s_dma = (li + 2) % NS, par = li & 1;
+    // iteration li (tile t = t_beg + li): GEMM1 reads slot (li + 1) % 3, the DMA fills slot (li + 2) % 3
+    uint32_t o_nxt = TB, o_dma = 2 * TB, o_cur = 0, soff_dma = tile_soff(t_beg + 2);
+    uint32_t p_off = 0;  // byte offset of P(t)'s parity
+    // dma: tile t + 2 exists and is fetched; tail: tile t + 1 is the split's last and may be the sweep's partial one
+    auto iter = [&](auto dma, auto tail, auto work) {
       DEC5_T(const unsigned long long tm0 = __builtin_amdgcn_s_memtime();)
       if (!(DEC5_ABL & (1 | 128))) wait_vmcnt<0>();
       DEC5_T(const unsigned long long tm1 = __builtin_amdgcn_s_memtime();)
       barrier();  // [L] tile t + 1 landed, P(t) published, GEMM2(t - 1) done
       DEC5_T(const unsigned long long tm2 = __builtin_amdgcn_s_memtime(); unsigned long long tm3 = tm2;)
-      if (t + 1 < t_end) {
-        const uint32_t soff_dma = tile_soff(t + 2);  // branch-free: past the split the pieces fill the free slot
-        gemm1(lds + nxt * TB, s_nx, [&](int ks) {
+      if constexpr (decltype(work)::value) {
+        const uint32_t lb_dma = ring0 + o_dma;
+        gemm1(lds + o_nxt, s_nx, [&](int ks) {
           const int kk = ks - DEC5_PDMA_AT;
-          if (!(DEC5_ABL & 1) && kk >= 0 && kk % DEC5_DMA_STRIDE == 0 && kk / DEC5_DMA_STRIDE < PA) issue_piece(soff_dma, s_dma, prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
+          if constexpr (decltype(dma)::value)
+            if (!(DEC5_ABL & 1) && kk >= 0 && kk % DEC5_DMA_STRIDE == 0 && kk / DEC5_DMA_STRIDE < PA)
+              dma_piece(lb_dma, soff_dma, prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
         });
         DEC5_T(tm3 = __builtin_amdgcn_s_memtime();)
-        mask_tail(s_nx, t + 1);
-        p_out(par ^ 1);
+        if constexpr (decltype(tail)::value)
+          if (tail_last()) mask_tail(s_nx);
+        p_off ^= kPPar;
+        p_out(p_off);
+        const uint32_t o = o_cur;
+        o_cur = o_nxt; o_nxt = o_dma; o_dma = o;
+        soff_dma += kTileStep;
       }
       DEC5_T(const unsigned long long tm4 = __builtin_amdgcn_s_memtime(); tacc[0] += tm1 - tm0; tacc[1] += tm2 - tm1;
              tacc[2] += tm3 - tm2; tacc[3] += tm4 - tm3; ++ntl;)
-    }
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
+    int rem = n_tiles;
+    for (; rem > 2; --rem) iter(yes, no, yes);
+    if (rem == 2) iter(no, yes, yes);
+    if (rem >= 1) iter(no, no, no);  // the split's last tile: its P went out in the iteration before
     wait_vmcnt<0>();
 #pragma unroll
     for (int uh = 0; uh < 2; ++uh) {
@@ -438,9 +488,12 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
     };
 #endif
     if (t_beg < t_end) {
+#pragma unroll
       for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg), 0, i, i == 0);
-      if (t_beg + 1 < t_end)
+      if (t_beg + 1 < t_end) {
+#pragma unroll
         for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+      }
       wait_vmcnt<0>();
 #if DEC5_RSTAGE
       if (t_beg + 2 < t_end)
@@ -480,8 +533,10 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
         const uint32_t soff_dma = tile_soff(dma ? t + 2 : t);
         gemm1(lds + nxt * TB, s_nx, [&](int ks) {
 #if DEC5_DMA_BURST
-          if (dma && ks == DEC5_PDMA_AT)
+          if (dma && ks == DEC5_PDMA_AT) {
+#pragma unroll
             for (int i = 0; i < PA; ++i) issue_piece(soff_dma, s_dma, i, i == 0);
+          }
 #else
           const int kk = ks - DEC5_PDMA_AT;
           if (dma && kk >= 0 && kk % DEC5_DMA_STRIDE == 0 && kk / DEC5_DMA_STRIDE < PA) issue_piece(soff_dma, s_dma, prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
@@ -519,7 +574,7 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   for (int d = 0; d < (WITH_O ? DB : 1); ++d)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-  constexpr int BH = 2;
+  constexpr int BH = DEC5_G2_AHEAD;
   auto rdT = [&](const unsigned char* buf, int i) {
     const int kh = i / DB, db = i % DB;
     const unsigned char* tt = buf + cseg + (kh << 12);
@@ -553,9 +608,12 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   };
   if constexpr (PB > 0) {
     if (t_beg < t_end) {
+#pragma unroll
       for (int i = PA; i < PW; ++i) issue_piece(tile_soff(t_beg), 0, i, i == PA);
-      if (t_beg + 1 < t_end)
+      if (t_beg + 1 < t_end) {
+#pragma unroll
         for (int i = PA; i < PW; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+      }
       wait_vmcnt<0>();
     }
   }
@@ -570,52 +628,64 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
     const int vo = ((p >> 1) & 1) ? vlane[1] : vlane[0];
     cst[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, (int)so, 0));
   };
-  auto c_write = [&](int slot_i) {
+  auto c_write = [&](uint32_t slot_off) {
 #pragma unroll
     for (int k = 0; k < PB; ++k)
-      *reinterpret_cast<uint4*>(lds + slot_i * TB + (q * PW + PA + k) * 1024 + lane * 16) = cst[k];
+      *reinterpret_cast<uint4*>(lds + slot_off + (q * PW + PA + k) * 1024 + lane * 16) = cst[k];
   };
 #endif
   barrier();  // [P0]
   if (DEC5_P32) barrier();  // [PX]
   barrier();  // [P1]
-  for (int64_t t = t_beg; t < t_end; ++t) {
-    const int li = (int)(t - t_beg);
-    const int cur = li % NS, s_dma = (li + 2) % NS, par = li & 1;
+  // iteration li (tile t = t_beg + li): GEMM2 reads slot li % 3, the DMA fills slot (li + 2) % 3 with tile t + 2
+  uint32_t o_cur = 0, o_nxt = TB, o_dma = 2 * TB, soff_dma = tile_soff(t_beg + 2);
+  uint32_t p_off = 0;  // byte offset of P(t)'s parity
+  int rem = n_tiles;
+  // P(t) in GEMM2's B layout: user col, positions 8 h .. 8 h + 7 of k-steps 0 and 1
+  const unsigned char* const pr0 = p_row(0, col) + 16 * h;
+  auto iter = [&](auto dma_t) {
+    constexpr bool dma = decltype(dma_t)::value && !(DEC5_ABL & 1);  // tile t + 2 exists and is fetched
     DEC5_T(const unsigned long long tm0 = __builtin_amdgcn_s_memtime();)
     if constexpr (PB > 0) if (!(DEC5_ABL & (1 | 128))) wait_vmcnt<0>();
 #if DEC5_CRSTAGE
-    if (li >= 1 && t + 1 < t_end) c_write((li + 1) % NS);  // tile t + 1, loaded in the previous iteration
+    if (rem < n_tiles && rem > 1) c_write(o_nxt);  // tile t + 1, loaded in the previous iteration
 #endif
     DEC5_T(const unsigned long long tm1 = __builtin_amdgcn_s_memtime();)
     if (!(DEC5_ABL & 2)) barrier();  // [L]
     DEC5_T(const unsigned long long tm2 = __builtin_amdgcn_s_memtime();)
-    // P(t) in GEMM2's B layout: user col, positions 8 h .. 8 h + 7 of k-steps 0 and 1
-    const uint4 pf0 = *reinterpret_cast<const uint4*>(p_row(par, col) + 16 * h);
-    const uint4 pf1 = *reinterpret_cast<const uint4*>(p_row(par, col) + 32 + 16 * h);
-    // DEC5_BFREE (A/B): issue the pieces of tile t + 2 unconditionally (past the split they fill the free slot)
-    const bool dma = !(DEC5_ABL & 1) && (DEC5_BFREE || t + 2 < t_end);
-    const uint32_t soff_dma = tile_soff(dma ? t + 2 : t);
+    const uint4 pf0 = *reinterpret_cast<const uint4*>(pr0 + p_off);
+    const uint4 pf1 = *reinterpret_cast<const uint4*>(pr0 + p_off + 32);
+    const uint32_t lb_dma = ring0 + o_dma;
 #if DEC5_CRSTAGE
-    const uint32_t soff_ld = tile_soff(t + 2 < t_end ? t + 2 : t);
+    const uint32_t soff_ld = rem > 2 ? soff_dma : soff_dma - 2 * kTileStep;
 #endif
-    gemm2(lds + cur * TB, pf0, pf1, [&](int i) {
+    gemm2(lds + o_cur, pf0, pf1, [&](int i) {
       const int ii = i - DEC5_CDMA_AT;
 #if DEC5_CRSTAGE
       if constexpr (PB > 0)
         if (ii >= 0 && ii < PB) c_load(soff_ld, ii);
 #elif DEC5_DMA_BURST
-      if constexpr (PB > 0)
-        if (dma && ii == 0)
-          for (int k = 0; k < PB; ++k) issue_piece(soff_dma, s_dma, PA + k, k == 0);
+      if constexpr (PB > 0 && dma)
+        if (ii == 0) {
+#pragma unroll
+          for (int k = 0; k < PB; ++k) dma_piece(lb_dma, soff_dma, PA + k, k == 0);
+        }
 #else
-      if constexpr (PB > 0)
-        if (dma && ii >= 0 && ii % DEC5_DMA_STRIDE == 0 && ii / DEC5_DMA_STRIDE < PB) issue_piece(soff_dma, s_dma, PA + prot(ii / DEC5_DMA_STRIDE, PB), ii == 0);
+      if constexpr (PB > 0 && dma)
+        if (ii >= 0 && ii % DEC5_DMA_STRIDE == 0 && ii / DEC5_DMA_STRIDE < PB)
+          dma_piece(lb_dma, soff_dma, PA + prot(ii / DEC5_DMA_STRIDE, PB), ii == 0);
 #endif
     });
+    const uint32_t o = o_cur;
+    o_cur = o_nxt; o_nxt = o_dma; o_dma = o;
+    soff_dma += kTileStep;
+    p_off ^= kPPar;
     DEC5_T(const unsigned long long tm3 = __builtin_amdgcn_s_memtime(); tacc[0] += tm1 - tm0; tacc[1] += tm2 - tm1;
            tacc[2] += tm3 - tm2; ++ntl;)
-  }
+  };
+  // DEC5_BFREE (A/B): the last two iterations issue pieces too (past the split they fill the free slot)
+  for (; rem > (DEC5_BFREE ? 0 : 2); --rem) iter(std::true_type{});
+  for (; rem > 0; --rem) iter(std::false_type{});
   if constexpr (PB > 0) wait_vmcnt<0>();
   if (DEC5_P32) barrier();  // [PE0]
   barrier();  // [E0]
@@ -744,10 +814,10 @@ __global__ void __launch_bounds__(512) k_dec5_f8(const float* __restrict__ U, in
     const uint32_t so = soff + (uint32_t)((q * PW + i) * 1024);
     if (fresh)
       asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                   :: "s"(lb), "v"(voff), "s"(rsrc), "s"(so) : "memory");
+                   :: "s"(lb), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
     else
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-                   :: "s"(lb), "v"(voff), "s"(rsrc), "s"(so) : "memory");
+                   :: "s"(lb), "v"(voff), "s"(rsrc), "s"(so) : "memory", "m0");
   };
   auto tile_soff = [&](int t) { return (uint32_t)__builtin_amdgcn_readfirstlane(t * TB8); };
   auto barrier = [&] {
@@ -990,9 +1060,12 @@ __global__ void __launch_bounds__(512) k_dec5_f8(const float* __restrict__ U, in
   };
   if constexpr (PB > 0) {
     if (t_beg < t_end) {
+#pragma unroll
       for (int i = PA; i < PW; ++i) issue_piece(tile_soff(t_beg), 0, i, i == PA);
-      if (t_beg + 1 < t_end)
+      if (t_beg + 1 < t_end) {
+#pragma unroll
         for (int i = PA; i < PW; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+      }
       wait_vmcnt<0>();
     }
   }

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../recommendation-system_amd"
 make -s lib
 mkdir -p ../build_var
 HIPCC=/opt/rocm/bin/hipcc
-$HIPCC --offload-arch=gfx950 -O3 -fPIC -std=c++17 -I../include -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form "$@" \
+$HIPCC --offload-arch=gfx950 -O3 -fPIC -std=c++17 -I../include -munsafe-fp-atomics -mllvm -amdgpu-mfma-vgpr-form -Wno-inline-asm "$@" \
   -c csrc/hvae_decoder5.hip -o ../build_var/dec5_$name.o
 objs=$(ls build/*.o | grep -v hvae_decoder5.o)
 $HIPCC --offload-arch=gfx950 -shared -fPIC -o ../build_var/libhvae_$name.so $objs ../build_var/dec5_$name.o
