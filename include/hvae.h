@@ -401,6 +401,39 @@ int64_t hvae_decoder_users_per_tile(int dtype, int64_t nb, int64_t N, int64_t D)
  * fp8 at 1024 are refused (HVAE_ERR_UNSUPPORTED from the decoder calls): registers and LDS, DESIGN.md section 7.
  * A bf16 / fp8 image is addressed in 32 bits, so N D < 2^30 (N < 2^20 items at D = 1024). */
 int hvae_decoder_supported(int dtype, int64_t D);
+/* Which sweep a decoder call runs (ABI 6, additive). Host arithmetic only: no HIP call, no allocation, and it
+ * answers on a machine without a GPU. hvae_decoder_fwd / _train launch from the same plan, so for a workspace of
+ * ws_bytes the answer is what they run; ws_bytes = SIZE_MAX gives the plan hvae_decoder_workspace sizes for. A
+ * shorter workspace gets fewer item splits (3/4 of the count until it fits). The product library plans bf16_v2
+ * (every served D but 768), bf16_v5 (768), fp8_ring, fp8_v5 (768) and f32; the others exist in the A/B build only.
+ * Returns HVAE_ERR_ARG for a NULL out, a negative size, a dtype that is none of the three or a ws_bytes the decoder
+ * calls refuse (HVAE_ERR_WORKSPACE there: below one split's need), and HVAE_ERR_UNSUPPORTED with sweep = none (the
+ * sizes filled in as hvae_decoder_workspace counts them) where hvae_decoder_supported is 0. */
+enum {
+  HVAE_DEC_SWEEP_NONE = 0,
+  HVAE_DEC_SWEEP_BF16_V1 = 1,  /* k_dec_bf16: transposed image copy (A/B)                         */
+  HVAE_DEC_SWEEP_BF16_V2 = 2,  /* k_dec2_bf16<D, ds, nw>                                          */
+  HVAE_DEC_SWEEP_BF16_V3 = 3,  /* k_dec3_bf16, D = 768 (A/B)                                      */
+  HVAE_DEC_SWEEP_BF16_V4 = 4,  /* k_dec4_bf16, D = 768, or 384 above 64 users (A/B)               */
+  HVAE_DEC_SWEEP_BF16_V5 = 5,  /* k_dec5_bf16, D = 768: producer / consumer waves                 */
+  HVAE_DEC_SWEEP_BF16_V5W = 6, /* k_dec5w_bf16, D = 384 (A/B)                                     */
+  HVAE_DEC_SWEEP_BF16_V6 = 7,  /* k_dec6_bf16, D = 768: 96 users per E tile, its own tasks (A/B)  */
+  HVAE_DEC_SWEEP_FP8_RING = 8, /* k_dec_fp8                                                       */
+  HVAE_DEC_SWEEP_FP8_V4 = 9,   /* k_dec4_f8, D = 768 (A/B)                                        */
+  HVAE_DEC_SWEEP_FP8_V5 = 10,  /* k_dec5_f8, D = 768                                              */
+  HVAE_DEC_SWEEP_F32 = 11      /* k_dec_f32                                                       */
+};
+typedef struct hvae_dec_plan {
+  int sweep;                /* HVAE_DEC_SWEEP_* */
+  int ds, nw;               /* the D split and the waves per block that select the bf16_v2 / fp8_ring instance
+                               (the other sweeps have one form each) */
+  int64_t users_per_block;  /* 96 for bf16_v6 */
+  int splits;               /* item splits; bf16_v6: of its task plan, as tiles_per_split and blocks */
+  int64_t tiles_per_split;
+  int64_t blocks;           /* the sweep's grid */
+  size_t workspace;         /* bytes this plan uses of the workspace */
+} hvae_dec_plan;
+int hvae_decoder_plan(int dtype, int64_t nb, int64_t N, int64_t D, size_t ws_bytes, hvae_dec_plan* out);
 /* *out = max_i ||E_i||_2 of an fp32 / bf16 [N, D] matrix (computed once: E is frozen). */
 int hvae_row_norm_max(int dtype, const void* E, int64_t N, int64_t D, float* out, void* stream);
 /* The train-step form: the streaming sweep above plus, in the same finalize

@@ -141,4 +141,12 @@ constexpr int LDS_BYTES = NS * TB + 2 * 2 * 32 * PST + 4 * 64 * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "k_dec5_bf16 LDS");
 
 }  // namespace dec5
+
+// Launchers of hvae_decoder5.hip (k_dec5_bf16, k_dec5_f8), called from the plan's dispatch in hvae_decoder.hip
+int dec5_launch(bool with_o, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
+                int splits, int64_t tiles_per_split, int64_t blocks, int* flag, float* m, float* l, float* O,
+                float* lse, int direct, hipStream_t st);
+int dec5_f8_launch(bool with_o, const float* U, int64_t ldu, const unsigned char* T8, const int* ke,
+                   const float* enorm, int64_t nb, int64_t N, int splits, int64_t tiles_per_split, int64_t blocks,
+                   int* flag, float* m, float* l, float* O, float* lse, int direct, hipStream_t st);
 }  // namespace hvae

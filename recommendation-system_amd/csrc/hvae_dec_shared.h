@@ -182,25 +182,43 @@ __device__ __forceinline__ int pack_fp8x4(float a, float b, float c, float d) {
 }
 
 // ------------------------------------------------------------- planning ---
+// The sweep a plan runs, by include/hvae.h's HVAE_DEC_SWEEP_* values (which name each one's kernel); the product
+// library plans bf16_v2, bf16_v5, fp8_ring, fp8_v5 and f32, the A/B build all of them
+enum class DecSweep : int { none, bf16_v1, bf16_v2, bf16_v3, bf16_v4, bf16_v5, bf16_v5w, bf16_v6, fp8_ring, fp8_v4,
+                            fp8_v5, f32 };
+static_assert((int)DecSweep::bf16_v6 == HVAE_DEC_SWEEP_BF16_V6 && (int)DecSweep::f32 == HVAE_DEC_SWEEP_F32, "hvae.h");
+
 struct DecPlan {
+  DecSweep sweep;
+  int ds;       // the D split of bf16_v2 (1, 2, or 4 at D = 1024) and fp8_ring (2 above 384)
+  int nw;       // bf16_v2's waves per block (4, or 8 with ds = 2 at D <= 384)
+  int64_t upb;  // users per block
   int splits;
   int64_t tiles_per_split;
   int64_t blocks;
-  size_t lds;
-  int v2;    // bf16 version-2 sweep (k_dec2_bf16)
-  int v3;    // bf16 version-3 sweep (k_dec3_bf16, D = 768)
-  int v4;    // bf16 version-4 sweep (k_dec4_bf16: D = 768 with 4 waves, D = 384 with 8)
-  int v5;    // bf16 version-5 sweep (k_dec5_bf16, D = 768: 8 waves, GEMM1 and GEMM2 on different waves)
-  int v6;    // bf16 version-6 sweep (k_dec6_bf16, D = 768: 96 users per E tile, task plan p6)
-  Dec6Plan p6;
-  int ds;    // its D split (1, 2, or 4 at D = 1024)
-  int nw;    // its waves per block (4, or 8 with ds = 2 at D <= 384)
-  int64_t upb;
+  Dec6Plan p6;  // bf16_v6's tasks (splits, tiles_per_split and blocks are then version 5's, its fallback)
+};
+
+// A/B overrides of the plan; the default is the product's, and the product build has no other
+struct DecAb {
+  int v1 = 0;                  // HVAE_DEC_V1=1: the version-1 bf16 sweep
+  int splits = 0;              // HVAE_DEC_SPLITS=k: k item splits
+  int ds = 0, nw = 0;          // HVAE_DEC_DS, HVAE_DEC_NW: bf16_v2's form at D <= 384
+  int v3 = 1, v4 = 1, v5 = 1;  // HVAE_DEC_V3 / V4 / V5=0: D = 768 stays on version 2 / 3 / 4
+  int v4_384 = 0;              // HVAE_DEC_V4_384=1: version 4 with 8 waves at D = 384 above 64 users
+  int v5w = 0;                 // HVAE_DEC_V5W=1: k_dec5w_bf16 where D = 384 runs bf16_v2 with ds = 1 (slower at
+                               // Syn-1M: 579-645 vs 520-531 us, profiles/r03_dec5w_vs_v2_syn1m.jsonl)
+  int v6 = 0;                  // HVAE_DEC_V6=1: version 6 above 64 users where its task plan succeeds
+  int f8v4 = 0, f8v5 = 1;      // HVAE_DEC_F8V4=1: k_dec4_f8; HVAE_DEC_F8V5=0: the D-split ring at D = 768
 };
 
 #if HVAE_AB
 // The retired sweeps (ab/hvae_decoder_ab.hip): version 1 at D <= 384, versions 3 and 4 at D = 768 (4 at 384 too),
 // the fp8 sweep with version 4's structure at D = 768. Same arguments as the product launchers.
+// ab/hvae_decoder5w.hip: dec5w_launch, with dec5_launch's arguments (hvae_dec5_shared.h).
+int dec5w_launch(bool with_o, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
+                 int splits, int64_t tiles_per_split, int64_t blocks, int* flag, float* m, float* l, float* O,
+                 float* lse, int direct, hipStream_t st);
 int ab_dec_v1(bool wo, int D, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
               const DecPlan& p, DecOut o, hipStream_t st);
 int ab_dec_v3(bool wo, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,

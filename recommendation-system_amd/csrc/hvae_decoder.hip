@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "hvae_common.h"
+#include "hvae_dec5_shared.h"
 #include "hvae_dec_shared.h"
 
 namespace hvae {
@@ -1553,122 +1554,41 @@ __global__ void __launch_bounds__(256) k_row_norm_max(int dtype, const void* __r
   if (lane == 0) atomicMax(out_bits, __float_as_uint(best));  // non-negative floats order as uints
 }
 
-
-// A/B switches (environment, read at plan time) exist only in variant builds (-DHVAE_AB=1, scripts/build_ab.sh);
-// the product library runs one sweep per (dtype, D): bf16 version 2 at D <= 384, 512 and 1024, version 5 at
-// D = 768, the fp8 ring, the fp32 sweep.
+// A/B switches (HVAE_DEC_* in the environment, all read at every plan) exist only in variant builds (-DHVAE_AB=1,
+// `make lib-ab`); the product library plans with DecAb's defaults: bf16 version 2 at every served D but 768,
+// version 5 there, the fp8 ring (version 5 at 768), the fp32 sweep.
+static DecAb dec_ab() {
+  DecAb ab;
 #if HVAE_AB
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && *v) ? atoi(v) : dflt;
-}
-
-// HVAE_DEC_V1=1 selects the version-1 bf16 sweep (transposed image copy), HVAE_DEC_SPLITS=k forces k item splits
-static bool dec_use_v1() {
-  static const int v = env_int("HVAE_DEC_V1", 0);
-  return v != 0;
-}
-static int dec_forced_splits() { return env_int("HVAE_DEC_SPLITS", 0); }
-
-static int dec_forced_ds() {
-  static const int v = env_int("HVAE_DEC_DS", 0);
-  return v;
-}
-
-static int dec_forced_nw() {
-  static const int v = env_int("HVAE_DEC_NW", 0);
-  return v;
-}
-#else
-static bool dec_use_v1() { return false; }
-static int dec_forced_splits() { return 0; }
-static int dec_forced_ds() { return 0; }
-static int dec_forced_nw() { return 0; }
-static int env_int(const char*, int dflt) { return dflt; }
+  auto env = [](const char* name, int dflt) {
+    const char* v = getenv(name);
+    return (v && *v) ? atoi(v) : dflt;
+  };
+  ab.v1 = env("HVAE_DEC_V1", ab.v1);
+  ab.splits = env("HVAE_DEC_SPLITS", ab.splits);
+  ab.ds = env("HVAE_DEC_DS", ab.ds);
+  ab.nw = env("HVAE_DEC_NW", ab.nw);
+  ab.v3 = env("HVAE_DEC_V3", ab.v3);
+  ab.v4 = env("HVAE_DEC_V4", ab.v4);
+  ab.v5 = env("HVAE_DEC_V5", ab.v5);
+  ab.v4_384 = env("HVAE_DEC_V4_384", ab.v4_384);
+  ab.v5w = env("HVAE_DEC_V5W", ab.v5w);
+  ab.v6 = env("HVAE_DEC_V6", ab.v6);
+  ab.f8v4 = env("HVAE_DEC_F8V4", ab.f8v4);
+  ab.f8v5 = env("HVAE_DEC_F8V5", ab.f8v5);
 #endif
-
-static bool v2_supported(int64_t D) {
-  return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
-}
-// HVAE_DEC_V3=0 keeps the version-2 sweep at D = 768 (A/B; read at every plan, so a test can switch it)
-static bool v3_supported(int64_t D) { return D == 768 && env_int("HVAE_DEC_V3", 1) != 0; }
-// HVAE_DEC_V4=0 keeps version 3 at D = 768 (A/B; read at every plan)
-static bool v4_supported(int64_t D) { return D == 768 && env_int("HVAE_DEC_V4", 1) != 0; }
-// HVAE_DEC_V4_384=1 runs version 4 with 8 waves at D = 384 (large batches) instead of version 2's DS = 1 sweep
-static bool v4_384(int64_t D, int64_t nb) { return D == 384 && nb > 64 && env_int("HVAE_DEC_V4_384", 0) != 0; }
-// version 5 (hvae_decoder5.hip: producer / consumer waves, two per SIMD) runs the bf16 sweep at D = 768 since
-// both use the conflict-free GEMM1 row map (2.5 % under version 4 at the Syn-10M shard); HVAE_DEC_V5=0 runs
-// version 4 (A/B; read at every plan)
-static bool v5_supported(int64_t D) { return D == 768 && env_int("HVAE_DEC_V5", 1) != 0; }
-int dec5_launch(bool with_o, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
-                int splits, int64_t tiles_per_split, int64_t blocks, int* flag, float* m, float* l, float* O,
-                float* lse, int direct, hipStream_t st);
-int dec5w_launch(bool with_o, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
-                 int splits, int64_t tiles_per_split, int64_t blocks, int* flag, float* m, float* l, float* O,
-                 float* lse, int direct, hipStream_t st);
-// HVAE_DEC_V5W=1 (A/B build) runs the d = 384 bf16 sweep of large batches as version 5's producer / consumer split
-// with 128 users per block (k_dec5w_bf16). It passes the decoder parity tests but measured slower than version 2's
-// DS = 1 sweep at Syn-1M (579-645 vs 520-531 us, profiles/r03_dec5w_vs_v2_syn1m.jsonl), so version 2 stays
-static bool v5w_supported(int64_t D) { return D == 384 && env_int("HVAE_DEC_V5W", 0) != 0; }
-int dec5_f8_launch(bool with_o, const float* U, int64_t ldu, const unsigned char* T8, const int* ke,
-                   const float* enorm, int64_t nb, int64_t N, int splits, int64_t tiles_per_split, int64_t blocks,
-                   int* flag, float* m, float* l, float* O, float* lse, int direct, hipStream_t st);
-
-static void dec_set_splits(DecPlan& p, int64_t tiles, int64_t s) {
-  s = std::max<int64_t>(1, std::min<int64_t>(s, std::min<int64_t>(tiles, kMaxSplits)));
-  p.tiles_per_split = std::max<int64_t>(1, cdiv(tiles, s));  // N = 0: one empty split
-  p.splits = (int)cdiv(tiles, p.tiles_per_split);
+  return ab;
 }
 
-static DecPlan dec_plan(int dtype, int64_t nb, int64_t N, int64_t D) {
-  DecPlan p{};
-  if (dtype == HVAE_FP8) {  // k_dec_fp8: 128 users per block (64 with the D split), 64-item tiles
-    p.ds = D > 384 ? 2 : 1;
-    p.upb = 128 / p.ds;
-    const int64_t nub = cdiv(nb, p.upb), tiles = cdiv(N, kF8TI);
-    int64_t s = cdiv(256, std::max<int64_t>(1, nub));  // nb = 0: a workspace query
-    s = std::min<int64_t>(s, std::max<int64_t>(1, tiles / 2));
-    s = std::min<int64_t>(s, std::max<int64_t>(1, N / std::max<int64_t>(1, 2 * nb)));
-    if (s >= 8) s = s / 8 * 8;
-    if (dec_forced_splits() > 0) s = dec_forced_splits();
-    dec_set_splits(p, tiles, s);
-    if (p.splits >= 8 && p.splits % 8 && dec_forced_splits() <= 0) dec_set_splits(p, tiles, (int64_t)p.splits / 8 * 8);
-    p.blocks = nub * p.splits;
-    return p;
+// The widths each dtype's sweeps are built for. Not served: fp32 at 768 / 1024 (k_dec_f32 over all of D spills),
+// fp8 at 1024 (no three-slot ring of 64 KiB tiles).
+static bool dec_serves(int dtype, int64_t D) {
+  switch (dtype) {
+    case HVAE_F32: return D == 32 || D == 64 || D == 128 || D == 256 || D == 384 || D == 512;
+    case HVAE_BF16: return D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024;
+    case HVAE_FP8: return D == 128 || D == 256 || D == 384 || D == 512 || D == 768;
+    default: return false;
   }
-  const bool bf = dtype == HVAE_BF16;
-  p.v2 = bf && !dec_use_v1() && v2_supported(D);
-  p.v3 = p.v2 && v3_supported(D);
-  p.v4 = (p.v3 && v4_supported(D)) || (p.v2 && v4_384(D, nb));
-  p.v5 = p.v4 && v5_supported(D);  // same users per block (64), splits and partial layout as version 4
-#if HVAE_AB  // HVAE_DEC_V6=1: version 6 (ab/hvae_decoder6.hip, 96 users per E tile) above 64 users
-  p.v6 = p.v5 && D == 768 && env_int("HVAE_DEC_V6", 0) != 0 && dec6_plan(nb, N, p.p6);
-#else
-  p.v6 = 0;
-#endif
-  p.ds = p.v2 && D == 1024 ? 4 : p.v2 && (D > 384 || nb <= 64) ? 2 : 1;  // 1024: quarters, 32 users per block
-  if (p.v2 && D <= 384 && (dec_forced_ds() == 1 || dec_forced_ds() == 2)) p.ds = dec_forced_ds();
-  p.nw = p.v2 && p.ds == 2 && nb > 64 && D <= 384 ? 8 : 4;
-  if (p.v2 && p.ds == 2 && D <= 384 && (dec_forced_nw() == 4 || dec_forced_nw() == 8)) p.nw = dec_forced_nw();
-  p.upb = bf ? (p.v4 && D == 384 ? 128 : (p.v3 || p.v5) ? 64 : p.v2 ? 32 * p.nw / p.ds : kBfUsersPerBlock)
-             : kF32UsersPerBlock;
-  const int64_t ti = bf ? kBfTI : kF32TI;
-  const int64_t target = bf ? 256 : 512;
-  const int64_t nub = cdiv(nb, p.upb), tiles = cdiv(N, ti);
-  int64_t s = cdiv(target, std::max<int64_t>(1, nub));
-  s = std::min<int64_t>(s, std::max<int64_t>(1, tiles / 2));
-  // each split writes nb (D + 2) floats of partials: keep them below ~2x the E bytes it streams
-  s = std::min<int64_t>(s, std::max<int64_t>(1, (bf ? N : 2 * N) / std::max<int64_t>(1, 2 * nb)));
-  if (s >= 8) s = s / 8 * 8;
-  if (dec_forced_splits() > 0) s = dec_forced_splits();
-  dec_set_splits(p, tiles, s);
-  if (p.splits >= 8 && p.splits % 8 && dec_forced_splits() <= 0) {  // keep "split shares an XCD" when possible
-    const int64_t s8 = (int64_t)p.splits / 8 * 8;
-    dec_set_splits(p, tiles, s8);
-  }
-  p.blocks = nub * p.splits;
-  p.lds = 0;
-  return p;
 }
 
 // workspace: flags [splits * nb] | partials m, l [2 splits * nb, padded to 16 B] and O [splits * nb * D]
@@ -1684,7 +1604,86 @@ static size_t dec_ws_bytes(int splits, int64_t nb, int64_t D) {
          (splits > 1 ? (dec_ml_floats(splits, nb) + (size_t)splits * nb * D) * sizeof(float) : 0) +
          (size_t)nb * D * sizeof(float);
 }
+// version 6: flags | m | l | O over the slot rows [p6.slots][96], then the O scratch of the other layouts
+static size_t dec6_ws_bytes(const Dec6Plan& q, int64_t nb, int64_t D) {
+  const size_t rows = (size_t)q.slots * kDec6Users;
+  return (size_t)cdiv((int64_t)(rows * sizeof(int)), 256) * 256 + rows * (2 + (size_t)D) * sizeof(float) +
+         (size_t)nb * D * sizeof(float);
+}
+// what plan p uses of the workspace (version 6's also fits version 5's, its fallback in a short workspace)
+static size_t plan_ws_bytes(const DecPlan& p, int64_t nb, int64_t D) {
+  const size_t base = dec_ws_bytes(p.splits, nb, D);
+  return p.sweep == DecSweep::bf16_v6 ? std::max(base, dec6_ws_bytes(p.p6, nb, D)) : base;
+}
 
+static void dec_set_splits(DecPlan& p, int64_t tiles, int64_t s) {
+  s = std::max<int64_t>(1, std::min<int64_t>(s, std::min<int64_t>(tiles, kMaxSplits)));
+  p.tiles_per_split = std::max<int64_t>(1, cdiv(tiles, s));  // N = 0: one empty split
+  p.splits = (int)cdiv(tiles, p.tiles_per_split);
+}
+
+// bf16: the sweep, its form and its users per block
+static void dec_plan_bf16(DecPlan& p, int64_t nb, int64_t D, const DecAb& ab) {
+  p.ds = 1, p.nw = 4, p.upb = kBfUsersPerBlock;  // version 1's, and what an unserved width is sized with
+  if (ab.v1 || !dec_serves(HVAE_BF16, D)) {
+    if (ab.v1 && D <= 384 && dec_serves(HVAE_BF16, D)) p.sweep = DecSweep::bf16_v1;
+    return;
+  }
+  p.ds = D == 1024 ? 4 : (D > 384 || nb <= 64) ? 2 : 1;  // 1024: quarters, 32 users per block
+  if (D <= 384 && (ab.ds == 1 || ab.ds == 2)) p.ds = ab.ds;
+  p.nw = p.ds == 2 && nb > 64 && D <= 384 ? 8 : 4;
+  if (p.ds == 2 && D <= 384 && (ab.nw == 4 || ab.nw == 8)) p.nw = ab.nw;
+  const bool v4_384 = D == 384 && nb > 64 && ab.v4_384;
+  if (D == 384 && p.ds == 1 && !v4_384 && ab.v5w) p.sweep = DecSweep::bf16_v5w, p.upb = 128;
+  else if (D == 768 && ab.v3 && ab.v4 && ab.v5) p.sweep = DecSweep::bf16_v5, p.upb = 64;
+  else if (D == 768 && ab.v3 && ab.v4) p.sweep = DecSweep::bf16_v4, p.upb = 64;
+  else if (v4_384) p.sweep = DecSweep::bf16_v4, p.upb = 128;
+  else if (D == 768 && ab.v3) p.sweep = DecSweep::bf16_v3, p.upb = 64;
+  else p.sweep = DecSweep::bf16_v2, p.upb = 32 * p.nw / p.ds;
+}
+
+// The plan a decoder call with a workspace of ws_bytes runs (SIZE_MAX: the one hvae_decoder_workspace sizes for).
+// Pure host arithmetic. An unserved (dtype, D) gets sweep none and is still sized.
+static DecPlan dec_plan(int dtype, int64_t nb, int64_t N, int64_t D, size_t ws_bytes, const DecAb& ab) {
+  DecPlan p{};
+  // tile items, blocks to aim for, and the items per user a split must stream: each split writes nb (D + 2)
+  // floats of partials, kept below ~2x the E bytes it streams
+  int64_t ti, target, per_user;
+  if (dtype == HVAE_FP8) {  // 128 users per block (64 with the D split)
+    p.ds = D > 384 ? 2 : 1, p.nw = 4, p.upb = 128 / p.ds;
+    if (dec_serves(dtype, D))
+      p.sweep = D != 768 ? DecSweep::fp8_ring : ab.f8v4 ? DecSweep::fp8_v4 : ab.f8v5 ? DecSweep::fp8_v5
+                                                                                     : DecSweep::fp8_ring;
+    ti = kF8TI, target = 256, per_user = N;
+  } else if (dtype == HVAE_BF16) {
+    dec_plan_bf16(p, nb, D, ab);
+    ti = kBfTI, target = 256, per_user = N;
+  } else {
+    p.ds = 1, p.nw = 4, p.upb = kF32UsersPerBlock;
+    if (dec_serves(dtype, D)) p.sweep = DecSweep::f32;
+    ti = kF32TI, target = 512, per_user = 2 * N;
+  }
+  const int64_t nub = cdiv(nb, p.upb), tiles = cdiv(N, ti);
+  int64_t s = cdiv(target, std::max<int64_t>(1, nub));  // nb = 0: a workspace query
+  s = std::min<int64_t>(s, std::max<int64_t>(1, tiles / 2));
+  s = std::min<int64_t>(s, std::max<int64_t>(1, per_user / std::max<int64_t>(1, 2 * nb)));
+  if (s >= 8) s = s / 8 * 8;
+  if (ab.splits > 0) s = ab.splits;
+  dec_set_splits(p, tiles, s);
+  if (p.splits >= 8 && p.splits % 8 && ab.splits <= 0)  // keep "split shares an XCD" when possible
+    dec_set_splits(p, tiles, (int64_t)p.splits / 8 * 8);
+  if (p.splits > 1 && ws_bytes < dec_ws_bytes(p.splits, nb, D)) {  // fewer splits that fit
+    int64_t fit = p.splits;
+    while (fit > 1 && ws_bytes < dec_ws_bytes((int)fit, nb, D)) fit = fit * 3 / 4;
+    dec_set_splits(p, tiles, fit);
+  }
+  p.blocks = nub * p.splits;
+  if constexpr (HVAE_AB != 0) {  // dec6_plan exists in the A/B build only (ab/hvae_decoder6.hip)
+    if (p.sweep == DecSweep::bf16_v5 && ab.v6 && dec6_plan(nb, N, p.p6) && ws_bytes >= dec6_ws_bytes(p.p6, nb, D))
+      p.sweep = DecSweep::bf16_v6;
+  }
+  return p;
+}
 
 template <int D, int DS, int NW, bool WO>
 static int launch_bf16_v2_nw(const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
@@ -1712,8 +1711,6 @@ static int launch_bf16_v2(const float* U, int64_t ldu, const void* E, const floa
   return launch_bf16_v2_nw<D, DS, 4, WO>(U, ldu, E, enorm, nb, N, p, o, st);
 }
 
-
-
 template <int D, bool WO>
 static int launch_fp8(const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
                       const DecPlan& p, DecOut o, hipStream_t st) {
@@ -1732,7 +1729,6 @@ static int launch_fp8(const float* U, int64_t ldu, const void* E, const float* e
   return HVAE_OK;
 }
 
-
 template <int D, bool WO>
 static int launch_f32(const float* U, int64_t ldu, const void* E, int64_t nb, int64_t N, const DecPlan& p,
                       DecOut o, hipStream_t st) {
@@ -1748,81 +1744,95 @@ static int launch_f32(const float* U, int64_t ldu, const void* E, int64_t nb, in
   return HVAE_OK;
 }
 
+// what the finalize merges and whether its grouped form runs: set by decoder_run's carve, replaced by version 6's
+struct DecFin {
+  FinArgs a;
+  bool grouped;
+};
+
+#if HVAE_AB
+// version 6 carves the workspace its own way -- flags | m | l | O over the slot rows [q.slots][96] -- and the
+// finalize merges each user's rows by the slot map
+static int dec6_sweep(bool wo, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb, int64_t N,
+                      const Dec6Plan& q, void* ws, float* O, DecFin& fin, hipStream_t st) {
+  const size_t rows = (size_t)q.slots * kDec6Users;
+  int* flag = (int*)ws;
+  float* pm = (float*)((char*)ws + (size_t)cdiv((int64_t)(rows * sizeof(int)), 256) * 256);
+  float* pl = pm + rows;
+  float* pO = wo ? pl + rows : nullptr;
+  FinArgs a{};
+  a.splits = q.S;
+  a.pm = pm; a.pl = pl; a.pO = pO;
+  a.flag = flag;
+  a.v6_upb = kDec6Users; a.v6_nub = q.nub; a.v6_S = q.S; a.v6_main = q.main; a.v6_P = q.P;
+  a.O_out = O;
+  fin = DecFin{a, q.X > 0 || q.S > 8};
+  return dec6_launch(wo, U, ldu, E, enorm, nb, N, q, flag, pm, pl, pO, st);
+}
+#endif
+
+// the launch of plan p's sweep (the 768 instances of k_dec_fp8 and k_dec2_bf16 are planned, and built, in the A/B
+// build only)
 template <bool WO>
 static int dispatch(int dtype, const float* U, int64_t ldu, const void* E, const float* enorm, int64_t nb,
-                    int64_t N, int64_t D, const DecPlan& p, DecOut o, hipStream_t st) {
-  if (dtype == HVAE_FP8) {
-    switch (D) {
-      case 128: return launch_fp8<128, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-      case 256: return launch_fp8<256, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-      case 384: return launch_fp8<384, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-      case 512: return launch_fp8<512, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-      case 768:
-#if HVAE_AB  // HVAE_DEC_F8V4=1 runs the version-4 structure, HVAE_DEC_F8V5=0 the D-split ring
-        if (env_int("HVAE_DEC_F8V4", 0) != 0) return ab_dec_f8v4(WO, U, ldu, E, enorm, nb, N, p, o, st);
-        if (env_int("HVAE_DEC_F8V5", 1) == 0) return launch_fp8<768, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-#endif
-        return dec5_f8_launch(WO, U, ldu, (const unsigned char*)E + f8_offset_bytes(N, 768),
-                              (const int*)((const char*)E + f8_tail_offset(N, 768)), enorm, nb, N, p.splits,
-                              p.tiles_per_split, p.blocks, o.flag, o.m, o.l, o.O, o.lse, o.direct, st);
-      default: break;
-    }
-#if HVAE_AB
-  } else if (dtype == HVAE_BF16 && p.v2 && p.ds == 1 && !p.v4 && D == 384 && v5w_supported(D)) {
-    return dec5w_launch(WO, U, ldu, E, enorm, nb, N, p.splits, p.tiles_per_split, p.blocks, o.flag, o.m, o.l, o.O,
-                        o.lse, o.direct, st);
-#endif
-  } else if (dtype == HVAE_BF16 && p.v5 && D == 768) {
-    return dec5_launch(WO, U, ldu, E, enorm, nb, N, p.splits, p.tiles_per_split, p.blocks, o.flag, o.m, o.l, o.O,
-                       o.lse, o.direct, st);
-#if HVAE_AB
-  } else if (dtype == HVAE_BF16 && p.v4 && D == 768) {
-    return ab_dec_v4(WO, 768, U, ldu, E, enorm, nb, N, p, o, st);
-  } else if (dtype == HVAE_BF16 && p.v4 && D == 384) {
-    return ab_dec_v4(WO, 384, U, ldu, E, enorm, nb, N, p, o, st);
-  } else if (dtype == HVAE_BF16 && p.v3 && D == 768) {
-    return ab_dec_v3(WO, U, ldu, E, enorm, nb, N, p, o, st);
-#endif
-  } else if (dtype == HVAE_BF16 && p.v2) {
-    if (p.ds == 1) {
+                    int64_t N, int64_t D, const DecPlan& p, DecOut o, void* ws, float* O, DecFin& fin,
+                    hipStream_t st) {
+#define DEC_ARGS U, ldu, E, enorm, nb, N, p, o, st
+#define DEC5_ARGS enorm, nb, N, p.splits, p.tiles_per_split, p.blocks, o.flag, o.m, o.l, o.O, o.lse, o.direct, st
+  switch (p.sweep) {
+    case DecSweep::fp8_ring:
       switch (D) {
-        case 64: return launch_bf16_v2<64, 1, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 128: return launch_bf16_v2<128, 1, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 256: return launch_bf16_v2<256, 1, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 384: return launch_bf16_v2<384, 1, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        default: break;
-      }
-    } else {
-      switch (D) {
-        case 64: return launch_bf16_v2<64, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 128: return launch_bf16_v2<128, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 256: return launch_bf16_v2<256, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 384: return launch_bf16_v2<384, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 512: return launch_bf16_v2<512, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-        case 1024:
-          if (p.ds == 4) return launch_bf16_v2<1024, 4, WO>(U, ldu, E, enorm, nb, N, p, o, st);
+        case 128: return launch_fp8<128, WO>(DEC_ARGS);
+        case 256: return launch_fp8<256, WO>(DEC_ARGS);
+        case 384: return launch_fp8<384, WO>(DEC_ARGS);
+        case 512: return launch_fp8<512, WO>(DEC_ARGS);
+        case 768:
+          if constexpr (HVAE_AB != 0) return launch_fp8<768, WO>(DEC_ARGS);
           break;
-#if HVAE_AB
-        case 768: return launch_bf16_v2<768, 2, WO>(U, ldu, E, enorm, nb, N, p, o, st);
-#endif
         default: break;
       }
-    }
+      break;
+    case DecSweep::fp8_v5:
+      return dec5_f8_launch(WO, U, ldu, (const unsigned char*)E + f8_offset_bytes(N, 768),
+                            (const int*)((const char*)E + f8_tail_offset(N, 768)), DEC5_ARGS);
+    case DecSweep::bf16_v5: return dec5_launch(WO, U, ldu, E, DEC5_ARGS);
+    case DecSweep::bf16_v2:  // ds: 1 or 2 up to 384, 2 at 512 and 768, 4 at 1024
+      switch (D) {
+        case 64: return p.ds == 1 ? launch_bf16_v2<64, 1, WO>(DEC_ARGS) : launch_bf16_v2<64, 2, WO>(DEC_ARGS);
+        case 128: return p.ds == 1 ? launch_bf16_v2<128, 1, WO>(DEC_ARGS) : launch_bf16_v2<128, 2, WO>(DEC_ARGS);
+        case 256: return p.ds == 1 ? launch_bf16_v2<256, 1, WO>(DEC_ARGS) : launch_bf16_v2<256, 2, WO>(DEC_ARGS);
+        case 384: return p.ds == 1 ? launch_bf16_v2<384, 1, WO>(DEC_ARGS) : launch_bf16_v2<384, 2, WO>(DEC_ARGS);
+        case 512: return launch_bf16_v2<512, 2, WO>(DEC_ARGS);
+        case 1024: return launch_bf16_v2<1024, 4, WO>(DEC_ARGS);
+        case 768:
+          if constexpr (HVAE_AB != 0) return launch_bf16_v2<768, 2, WO>(DEC_ARGS);
+          break;
+        default: break;
+      }
+      break;
+    case DecSweep::f32:
+      switch (D) {
+        case 32: return launch_f32<32, WO>(U, ldu, E, nb, N, p, o, st);
+        case 64: return launch_f32<64, WO>(U, ldu, E, nb, N, p, o, st);
+        case 128: return launch_f32<128, WO>(U, ldu, E, nb, N, p, o, st);
+        case 256: return launch_f32<256, WO>(U, ldu, E, nb, N, p, o, st);
+        case 384: return launch_f32<384, WO>(U, ldu, E, nb, N, p, o, st);
+        case 512: return launch_f32<512, WO>(U, ldu, E, nb, N, p, o, st);
+        default: break;
+      }
+      break;
 #if HVAE_AB
-  } else if (dtype == HVAE_BF16) {
-    if (D == 64 || D == 128 || D == 256 || D == 384) return ab_dec_v1(WO, (int)D, U, ldu, E, enorm, nb, N, p, o, st);
+    case DecSweep::bf16_v1: return ab_dec_v1(WO, (int)D, DEC_ARGS);
+    case DecSweep::bf16_v3: return ab_dec_v3(WO, DEC_ARGS);
+    case DecSweep::bf16_v4: return ab_dec_v4(WO, (int)D, DEC_ARGS);
+    case DecSweep::bf16_v5w: return dec5w_launch(WO, U, ldu, E, DEC5_ARGS);
+    case DecSweep::bf16_v6: return dec6_sweep(WO, U, ldu, E, enorm, nb, N, p.p6, ws, O, fin, st);
+    case DecSweep::fp8_v4: return ab_dec_f8v4(WO, DEC_ARGS);
 #endif
-  } else if (dtype != HVAE_BF16) {
-    switch (D) {
-      case 32: return launch_f32<32, WO>(U, ldu, E, nb, N, p, o, st);
-      case 64: return launch_f32<64, WO>(U, ldu, E, nb, N, p, o, st);
-      case 128: return launch_f32<128, WO>(U, ldu, E, nb, N, p, o, st);
-      case 256: return launch_f32<256, WO>(U, ldu, E, nb, N, p, o, st);
-      case 384: return launch_f32<384, WO>(U, ldu, E, nb, N, p, o, st);
-      case 512: return launch_f32<512, WO>(U, ldu, E, nb, N, p, o, st);
-      default: break;
-    }
+    default: break;
   }
+#undef DEC_ARGS
+#undef DEC5_ARGS
   HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_decoder_fwd: no %s kernel for D=%lld",
             dtype == HVAE_FP8 ? "fp8" : dtype == HVAE_BF16 ? "bf16" : "f32", (long long)D);
 }
@@ -1831,14 +1841,8 @@ static int dispatch(int dtype, const float* U, int64_t ldu, const void* E, const
 
 using namespace hvae;
 
-
-extern "C" int hvae_decoder_supported(int dtype, int64_t D) {
-  // not served: fp32 at 768 / 1024 (k_dec_f32 over all of D spills), fp8 at 1024 (no three-slot ring of 64 KiB tiles)
-  if (dtype == HVAE_BF16)
-    return D == 64 || D == 128 || D == 256 || D == 384 || ((D == 512 || D == 768 || D == 1024) && !dec_use_v1());
-  if (dtype == HVAE_F32) return D == 32 || D == 64 || D == 128 || D == 256 || D == 384 || D == 512;
-  if (dtype == HVAE_FP8) return D == 128 || D == 256 || D == 384 || D == 512 || D == 768;
-  return 0;
+extern "C" int hvae_decoder_supported(int dtype, int64_t D) {  // whether a sweep is planned depends on no size
+  return dec_plan(dtype, 1, 1, D, SIZE_MAX, dec_ab()).sweep != DecSweep::none;
 }
 
 extern "C" int hvae_row_norm_max(int dtype, const void* E, int64_t N, int64_t D, float* out, void* stream) {
@@ -1863,7 +1867,7 @@ extern "C" int hvae_decoder_image(int dtype, const float* E32, int64_t N, int64_
   HVAE_REQUIRE(dtype == HVAE_BF16 || dtype == HVAE_F32 || dtype == HVAE_FP8, "hvae_decoder_image: bad dtype");
   hipStream_t st = as_stream(stream);
   if (dtype == HVAE_FP8) {
-    HVAE_REQUIRE((D == 128 || D == 256 || D == 384 || D == 512 || D == 768) && N * D * 2 < (1ll << 31),
+    HVAE_REQUIRE(dec_serves(HVAE_FP8, D) && N * D * 2 < (1ll << 31),
                  "hvae_decoder_image: fp8 needs D in {128, 256, 384, 512, 768} and N D < 2^30");
     const int64_t ntiles = cdiv(N, kF8TI);
     unsigned* amax = (unsigned*)((char*)out + f8_tail_offset(N, D) + 128);  // scratch word of the tail
@@ -1891,128 +1895,33 @@ extern "C" int hvae_decoder_image(int dtype, const float* E32, int64_t N, int64_
   return HVAE_OK;
 }
 
-// version 6: flags | m | l | O over the slot rows [p6.slots][96], then the O scratch of the other layouts (the
-// workspace also fits version 5's, the fallback when a caller's workspace is short)
-static size_t dec6_ws_bytes(const Dec6Plan& q, int64_t nb, int64_t D) {
-  const size_t rows = (size_t)q.slots * kDec6Users;
-  return (size_t)cdiv((int64_t)(rows * sizeof(int)), 256) * 256 + rows * (2 + (size_t)D) * sizeof(float) +
-         (size_t)nb * D * sizeof(float);
-}
-static size_t plan_ws_bytes(const DecPlan& p, int64_t nb, int64_t D) {
-  const size_t base = dec_ws_bytes(p.splits, nb, D);
-  return p.v6 ? std::max(base, dec6_ws_bytes(p.p6, nb, D)) : base;
+extern "C" int hvae_decoder_plan(int dtype, int64_t nb, int64_t N, int64_t D, size_t ws_bytes, hvae_dec_plan* out) {
+  HVAE_REQUIRE(out && nb >= 0 && N >= 0 && D >= 0, "hvae_decoder_plan: negative size / null out");
+  HVAE_REQUIRE(dtype == HVAE_BF16 || dtype == HVAE_F32 || dtype == HVAE_FP8, "hvae_decoder_plan: bad dtype");
+  const DecPlan p = dec_plan(dtype, nb, N, D, ws_bytes, dec_ab());
+  const bool v6 = p.sweep == DecSweep::bf16_v6;
+  *out = hvae_dec_plan{(int)p.sweep, p.ds, p.nw, v6 ? kDec6Users : p.upb, v6 ? p.p6.S : p.splits,
+                       v6 ? p.p6.tps : p.tiles_per_split, v6 ? p.p6.grid : p.blocks, plan_ws_bytes(p, nb, D)};
+  HVAE_REQUIRE(ws_bytes >= dec_ws_bytes(1, nb, D), "hvae_decoder_plan: workspace %zu < %zu", ws_bytes,
+               dec_ws_bytes(1, nb, D));
+  if (p.sweep == DecSweep::none) HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_decoder_plan: no sweep for D=%lld", (long long)D);
+  return HVAE_OK;
 }
 
 extern "C" int64_t hvae_decoder_users_per_tile(int dtype, int64_t nb, int64_t N, int64_t D) {
   if (nb <= 0 || N <= 0 || D <= 0) return 0;
-  const DecPlan p = dec_plan(dtype, nb, N, D);
-  return p.v6 ? kDec6Users : std::min<int64_t>(p.upb, nb);
+  const DecPlan p = dec_plan(dtype, nb, N, D, SIZE_MAX, dec_ab());
+  return p.sweep == DecSweep::bf16_v6 ? kDec6Users : std::min<int64_t>(p.upb, nb);
 }
 
 extern "C" size_t hvae_decoder_workspace(int dtype, int64_t nb, int64_t N, int64_t D) {
-  const DecPlan p = dec_plan(dtype, nb, N, D);
-  return plan_ws_bytes(p, nb, D);
+  return plan_ws_bytes(dec_plan(dtype, nb, N, D, SIZE_MAX, dec_ab()), nb, D);
 }
-
-static int decoder_finalize(FinArgs& a, const float* U, int64_t ldu, const void* E, const float* E32,
-                            const hvae_csr_batch* x, int64_t nb, int64_t N, int64_t D, float scale, float* lse,
-                            float* recon_rows, float* dU, const float* kl_rows, float beta, const float* beta_dev,
-                            float* loss3, double* accum3, bool grouped, hipStream_t st);
 
 // the finalize's 16-B column form: every row operand it reads or writes starts 16-B aligned
 static bool fin_v4(const FinArgs& a) {
   auto al = [](const void* p) { return ((uintptr_t)p % 16) == 0; };
   return a.D % 4 == 0 && a.ldu % 4 == 0 && al(a.U) && al(a.pO) && al(a.O_in) && al(a.O_out) && al(a.E32) && al(a.dU);
-}
-
-// flash sweep + finalize; csr / recon_rows / dU optional
-static int decoder_run(int dtype, const float* U, int64_t ldu, const void* E, const float* e_maxnorm,
-                       const float* E32, const hvae_csr_batch* x, int64_t nb, int64_t N, int64_t D, float scale,
-                       float* lse, float* O, float* recon_rows, float* dU, const float* kl_rows, float beta,
-                       const float* beta_dev, float* loss3, double* accum3, void* ws, size_t ws_bytes,
-                       hipStream_t st) {
-  HVAE_REQUIRE(dtype == HVAE_BF16 || dtype == HVAE_F32 || dtype == HVAE_FP8, "hvae decoder: bad dtype");
-  HVAE_REQUIRE(U && E && lse && N > 0 && D > 0 && ldu >= D, "hvae decoder: bad args");
-  HVAE_REQUIRE(dtype == HVAE_F32 || e_maxnorm, "hvae decoder: bf16 / fp8 need e_maxnorm");
-  HVAE_REQUIRE(D <= 1024, "hvae decoder: D > 1024 unsupported");
-  HVAE_REQUIRE(ldu % 4 == 0 && ((uintptr_t)U % 16) == 0 && ((uintptr_t)E % 16) == 0 &&
-                   (!O || ((uintptr_t)O % 16) == 0),
-               "hvae decoder: U/E/O must be 16-B aligned with ldu %% 4 == 0");
-  HVAE_REQUIRE(N < (1ll << 31), "hvae decoder: N too large");
-  HVAE_REQUIRE(dtype == HVAE_F32 || N * D * 2 < (1ll << 31), "hvae decoder: bf16 / fp8 E image over 2 GiB");
-  HVAE_REQUIRE(!x || (E32 && x->row_ptr && x->nb == nb && x->n_items == N), "hvae decoder: bad CSR batch");
-  if (nb == 0) return HVAE_OK;
-  DecPlan p = dec_plan(dtype, nb, N, D);
-  if (!ws || ws_bytes < dec_ws_bytes(1, nb, D))
-    HVAE_FAIL(HVAE_ERR_WORKSPACE, "hvae decoder: workspace %zu < %zu", ws_bytes, dec_ws_bytes(1, nb, D));
-  if (p.splits > 1 && ws_bytes < dec_ws_bytes(p.splits, nb, D)) {  // fewer splits that fit
-    int64_t fit = p.splits;
-    while (fit > 1 && ws_bytes < dec_ws_bytes((int)fit, nb, D)) fit = fit * 3 / 4;
-    const int64_t tiles = cdiv(N, dtype == HVAE_FP8 ? kF8TI : dtype == HVAE_BF16 ? kBfTI : kF32TI);
-    dec_set_splits(p, tiles, fit);
-    p.blocks = cdiv(nb, p.upb) * p.splits;
-  }
-  const bool bf = dtype != HVAE_F32;  // fixed-offset sweeps (bf16, fp8): flags, bf16 E for the exact fixup
-  const bool want_o = O || dU;
-  FinArgs a{};
-#if HVAE_AB
-  if (p.v6 && ws_bytes < dec6_ws_bytes(p.p6, nb, D)) p.v6 = 0;
-  if (p.v6) {  // version 6: slot-row partials, merged per user by the finalize's slot map
-    const Dec6Plan& q = p.p6;
-    const size_t rows = (size_t)q.slots * kDec6Users;
-    char* w6 = (char*)ws;
-    int* flag6 = (int*)w6;
-    w6 += (size_t)cdiv((int64_t)(rows * sizeof(int)), 256) * 256;
-    float* pm = (float*)w6;
-    float* pl = pm + rows;
-    float* pO = pl + rows;
-    int rc;
-    {
-      ProbeScope probe("decoder_sweep", st);
-      rc = dec6_launch(want_o, U, ldu, E, e_maxnorm, nb, N, q, flag6, pm, pl, want_o ? pO : nullptr, st);
-    }
-    if (rc) return rc;
-    a.splits = q.S;
-    a.pm = pm; a.pl = pl; a.pO = want_o ? pO : nullptr;
-    a.flag = flag6;
-    a.v6_upb = kDec6Users; a.v6_nub = q.nub; a.v6_S = q.S; a.v6_main = q.main; a.v6_P = q.P;
-    a.O_out = O;
-    return decoder_finalize(a, U, ldu, E, E32, x, nb, N, D, scale, lse, recon_rows, dU, kl_rows, beta, beta_dev,
-                            loss3, accum3, q.X > 0 || q.S > 8, st);
-  }
-#endif
-  char* w = (char*)ws;
-  DecOut o{};
-  o.flag = (int*)w;
-  w += dec_flag_bytes(p.splits, nb);
-  float* o_scratch = nullptr;
-  if (p.splits == 1) {
-    o.direct = 1;
-    o.lse = lse;
-    o.O = O ? O : (want_o ? (float*)w : nullptr);
-    o_scratch = o.O;
-  } else {
-    float* base = (float*)w;
-    o.direct = 0;
-    o.m = base;
-    o.l = base + (size_t)p.splits * nb;
-    o.O = base + dec_ml_floats(p.splits, nb);
-  }
-  int rc;
-  {
-    ProbeScope probe("decoder_sweep", st);
-    rc = want_o ? dispatch<true>(dtype, U, ldu, E, e_maxnorm, nb, N, D, p, o, st)
-                  : dispatch<false>(dtype, U, ldu, E, e_maxnorm, nb, N, D, p, o, st);
-  }
-  if (rc) return rc;
-  if (p.splits == 1 && !bf && !x) return HVAE_OK;  // fp32 single split: the sweep wrote lse / O already
-  a.splits = p.splits;
-  if (p.splits > 1) { a.pm = o.m; a.pl = o.l; a.pO = want_o ? o.O : nullptr; }
-  else { a.lse_in = lse; a.O_in = o_scratch; }
-  a.flag = bf ? o.flag : nullptr;
-  a.O_out = O ? O : (p.splits == 1 ? o_scratch : nullptr);
-  return decoder_finalize(a, U, ldu, E, E32, x, nb, N, D, scale, lse, recon_rows, dU, kl_rows, beta, beta_dev, loss3,
-                          accum3, p.splits > 8, st);
 }
 
 // the finalize launch of decoder_run (a's partial / direct inputs and O_out set by the caller)
@@ -2047,6 +1956,64 @@ static int decoder_finalize(FinArgs& a, const float* U, int64_t ldu, const void*
   }
   HVAE_LAUNCH_CHECK("k_dec_finalize");
   return HVAE_OK;
+}
+
+// flash sweep + finalize; csr / recon_rows / dU optional
+static int decoder_run(int dtype, const float* U, int64_t ldu, const void* E, const float* e_maxnorm,
+                       const float* E32, const hvae_csr_batch* x, int64_t nb, int64_t N, int64_t D, float scale,
+                       float* lse, float* O, float* recon_rows, float* dU, const float* kl_rows, float beta,
+                       const float* beta_dev, float* loss3, double* accum3, void* ws, size_t ws_bytes,
+                       hipStream_t st) {
+  HVAE_REQUIRE(dtype == HVAE_BF16 || dtype == HVAE_F32 || dtype == HVAE_FP8, "hvae decoder: bad dtype");
+  HVAE_REQUIRE(U && E && lse && N > 0 && D > 0 && ldu >= D, "hvae decoder: bad args");
+  HVAE_REQUIRE(dtype == HVAE_F32 || e_maxnorm, "hvae decoder: bf16 / fp8 need e_maxnorm");
+  HVAE_REQUIRE(D <= 1024, "hvae decoder: D > 1024 unsupported");
+  HVAE_REQUIRE(ldu % 4 == 0 && ((uintptr_t)U % 16) == 0 && ((uintptr_t)E % 16) == 0 &&
+                   (!O || ((uintptr_t)O % 16) == 0),
+               "hvae decoder: U/E/O must be 16-B aligned with ldu %% 4 == 0");
+  HVAE_REQUIRE(N < (1ll << 31), "hvae decoder: N too large");
+  HVAE_REQUIRE(dtype == HVAE_F32 || N * D * 2 < (1ll << 31), "hvae decoder: bf16 / fp8 E image over 2 GiB");
+  HVAE_REQUIRE(!x || (E32 && x->row_ptr && x->nb == nb && x->n_items == N), "hvae decoder: bad CSR batch");
+  if (nb == 0) return HVAE_OK;
+  if (!ws || ws_bytes < dec_ws_bytes(1, nb, D))
+    HVAE_FAIL(HVAE_ERR_WORKSPACE, "hvae decoder: workspace %zu < %zu", ws_bytes, dec_ws_bytes(1, nb, D));
+  const DecPlan p = dec_plan(dtype, nb, N, D, ws_bytes, dec_ab());
+  const bool bf = dtype != HVAE_F32;  // fixed-offset sweeps (bf16, fp8): flags, bf16 E for the exact fixup
+  const bool want_o = O || dU;
+  // carve: the sweep's outputs, and what the finalize reads of them
+  char* w = (char*)ws;
+  DecOut o{};
+  DecFin fin{FinArgs{}, p.splits > 8};
+  FinArgs& a = fin.a;
+  o.flag = (int*)w;
+  w += dec_flag_bytes(p.splits, nb);
+  a.splits = p.splits;
+  a.flag = bf ? o.flag : nullptr;
+  if (p.splits == 1) {
+    o.direct = 1;
+    o.lse = lse;
+    o.O = O ? O : (want_o ? (float*)w : nullptr);
+    a.lse_in = lse;
+    a.O_in = a.O_out = o.O;
+  } else {
+    float* base = (float*)w;
+    o.direct = 0;
+    o.m = base;
+    o.l = base + (size_t)p.splits * nb;
+    o.O = base + dec_ml_floats(p.splits, nb);
+    a.pm = o.m; a.pl = o.l; a.pO = want_o ? o.O : nullptr;
+    a.O_out = O;
+  }
+  int rc;
+  {
+    ProbeScope probe("decoder_sweep", st);
+    rc = want_o ? dispatch<true>(dtype, U, ldu, E, e_maxnorm, nb, N, D, p, o, ws, O, fin, st)
+                : dispatch<false>(dtype, U, ldu, E, e_maxnorm, nb, N, D, p, o, ws, O, fin, st);
+  }
+  if (rc) return rc;
+  if (p.splits == 1 && !bf && !x) return HVAE_OK;  // fp32 single split: the sweep wrote lse / O already
+  return decoder_finalize(a, U, ldu, E, E32, x, nb, N, D, scale, lse, recon_rows, dU, kl_rows, beta, beta_dev, loss3,
+                          accum3, fin.grouped, st);
 }
 
 extern "C" int hvae_decoder_fwd(int dtype, const float* U, int64_t ldu, const void* E, const float* e_maxnorm,

@@ -79,6 +79,16 @@ class GemmPlan(C.Structure):  # hvae_gemm_plan
                 ("long_k", cint), ("vec_a", cint), ("vec_b", cint)]
 
 
+class DecPlan(C.Structure):  # hvae_dec_plan
+    _fields_ = [("sweep", cint), ("ds", cint), ("nw", cint), ("users_per_block", i64), ("splits", cint),
+                ("tiles_per_split", i64), ("blocks", i64), ("workspace", sz)]
+
+
+# include/hvae.h HVAE_DEC_SWEEP_*, by value
+DEC_SWEEPS = ("none", "bf16_v1", "bf16_v2", "bf16_v3", "bf16_v4", "bf16_v5", "bf16_v5w", "bf16_v6", "fp8_ring",
+              "fp8_v4", "fp8_v5", "f32")
+
+
 class MlpRows(C.Structure):  # hvae_mlp_rows
     _fields_ = [
         ("nb", i64), ("H", i64), ("L", i64), ("D", i64),
@@ -162,6 +172,7 @@ SIGNATURES = {
     "hvae_decoder_workspace": (sz, [cint, i64, i64, i64]),
     "hvae_decoder_users_per_tile": (i64, [cint, i64, i64, i64]),
     "hvae_decoder_supported": (cint, [cint, i64]),
+    "hvae_decoder_plan": (cint, [cint, i64, i64, i64, sz, P(DecPlan)]),
     "hvae_row_norm_max": (cint, [cint, vp, i64, i64, vp, vp]),
     "hvae_decoder_bwd": (cint, [P(CsrBatch), vp, i64, vp, i64, vp, vp, f32, vp, vp, vp]),
     "hvae_decoder_train": (cint, [cint, vp, i64, vp, vp, vp, P(CsrBatch), i64, f32, vp, vp, vp, vp, vp, f32, vp,

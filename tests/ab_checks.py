@@ -45,6 +45,15 @@ def _maxrel(a, b):
     return float((a - b).abs().max() / max(b.abs().max().item(), 1e-30))
 
 
+def _sweep(dtype, nb, N, D):
+    """The sweep hvae_decoder_plan names for a call with the whole workspace, under the environment as it is now."""
+    import ctypes as C
+    from hvae._lib import DEC_SWEEPS, DecPlan, check, lib
+    p = DecPlan()
+    check(lib().hvae_decoder_plan(dtype, nb, N, D, 2 ** 64 - 1, C.byref(p)), "hvae_decoder_plan")
+    return DEC_SWEEPS[p.sweep]
+
+
 def test_decoder_d768_versions_agree(ops, dev, monkeypatch):
     """Versions 5 (GEMM1 and GEMM2 on different waves, the product sweep), 4 (item-split GEMM1, one barrier
     per tile) and 3 (item-half softmax ownership) against version 2 (whole-tile softmax in both waves) of the
@@ -66,6 +75,7 @@ def test_decoder_d768_versions_agree(ops, dev, monkeypatch):
         monkeypatch.setenv("HVAE_DEC_V3", v3)
         monkeypatch.setenv("HVAE_DEC_V4", v4)
         monkeypatch.setenv("HVAE_DEC_V5", v5)
+        assert _sweep(img.dtype, nb, N, D) == "bf16_" + name  # the four settings run four different kernels
         out[name] = ops.decoder_train(xd, U, img, enorm, E, 1.0 / nb, want_o=True)
     l2, o2, r2, d2 = out["v2"]
     for name in ("v5", "v4", "v3"):
@@ -86,6 +96,8 @@ def test_decoder_fp8_v4_structure(ops, dev, nb, N, variant, monkeypatch):
         monkeypatch.setenv("HVAE_DEC_F8V4", "1")
     else:
         monkeypatch.setenv("HVAE_DEC_F8V5", "0")
+    from hvae import _lib
+    assert _sweep(_lib.HVAE_FP8, nb, N, D) == ("fp8_v4" if variant == "F8V4" else "fp8_ring")
     E = torch.as_tensor(synth_embeddings(N, D, seed=N))
     g = torch.Generator().manual_seed(nb)
     U = torch.randn(nb, D, generator=g) * 3.0
@@ -122,6 +134,7 @@ def test_decoder_d384_v5w_agrees_v2(ops, dev, nb, N, monkeypatch):
     out = {}
     for v in ("1", "0"):
         monkeypatch.setenv("HVAE_DEC_V5W", v)
+        assert _sweep(img.dtype, nb, N, D) == ("bf16_v5w" if v == "1" else "bf16_v2")
         out[v] = ops.decoder_train(xd, U, img, enorm, E, 1.0 / nb, want_o=True)
     (la, oa, ra, da), (lb, ob, rb, db) = out["1"], out["0"]
     assert (la - lb).abs().max() < 1e-4
@@ -197,6 +210,7 @@ def test_decoder_bf16_d768_v6_tasks(ops, dev, nb, N, monkeypatch):
     dt, _, Eh = ops._dec_operand(Ek)
     need = int(lib().hvae_decoder_workspace(dt, nb, N, D))
     assert int(lib().hvae_decoder_users_per_tile(dt, nb, N, D)) == 96  # the plan took version 6
+    assert _sweep(dt, nb, N, D) == "bf16_v6"
     ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=dev)
     lse3, O3 = torch.empty_like(lse), torch.empty_like(O)
     check(lib().hvae_decoder_fwd(dt, ptr(U), U.stride(0), ptr(Eh), ptr(enorm), nb, N, D, ptr(lse3), ptr(O3), ptr(ws),
