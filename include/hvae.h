@@ -631,6 +631,40 @@ int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, const float
                     const float* e32_maxnorm, int64_t N, int64_t D, const hvae_csr_batch* exclude,
                     int64_t R, int64_t K, int32_t* idx, float* val, int32_t* flag, void* ws,
                     size_t ws_bytes, void* stream);
+/* What a hvae_topk_fused call launches and where it keeps its state (ABI 6, additive). Host arithmetic only: no HIP
+ * call, no allocation, and it answers on a machine without a GPU. hvae_topk_fused and hvae_topk_fused_workspace run
+ * from the same plan, so the answer is what they do for these arguments. The product library plans the LDS scans
+ * wherever D % 128 == 0 and the global-load scan (with wave_users = 1) at D = 64 only; the global-load scan at the
+ * other widths, wave_users = 0 and another tau period exist in the A/B build only. Every field is filled in whatever
+ * the return value (an unserved width is sized as hvae_topk_fused_workspace sizes it). Returns HVAE_ERR_UNSUPPORTED
+ * for a width or K that is not served (and from the A/B build for the global-load scan at D = 1024), HVAE_ERR_ARG for
+ * a NULL out, R < 0, N <= 0, K <= 0, K > N, N >= 2^31 - 1, or an LDS scan whose split of the bf16 E would reach 2^31
+ * bytes; hvae_topk_fused returns the same codes. */
+enum {
+  HVAE_TOPK_SCAN_GLOBAL = 0,  /* k_topk_scan: E fragments straight from global memory           */
+  HVAE_TOPK_SCAN_LDS = 1,     /* k_topk_scan_lds: E tiles by LDS-DMA, one wave per user group   */
+  HVAE_TOPK_SCAN_LDS_KH2 = 2  /* k_topk_scan_lds at D = 1024: the k axis in halves over a pair  */
+};
+typedef struct hvae_topk_plan {
+  int scan;                 /* HVAE_TOPK_SCAN_* */
+  int wave_users;           /* 1: a block's waves take different users over the same tiles; 0: one user group,
+                               the waves split the tiles (global-load scan, A/B) */
+  int block_users;          /* users per scan block: 128, 64 at D = 1024, 32 with wave_users = 0 */
+  int splits;               /* item splits of the scan */
+  int64_t tiles_per_split;  /* 32-item tiles of each of the first full_splits splits; the others take one fewer */
+  int full_splits;          /* so the ceil(N / 32) tiles are dealt evenly: no split is empty while tiles >= splits */
+  int nseg;                 /* candidate segments per user: splits x 2 (x 8 with wave_users = 0) */
+  int64_t blocks;           /* the scan's grid: ceil(R / block_users) x splits */
+  int64_t seed_blocks;      /* the seed pass's grid: ceil(R / 32) */
+  int nsample;              /* sampled tiles of the seed pass (<= 128) */
+  int64_t stride;           /* in tiles, between them */
+  int tau_period;           /* tiles between reads of the other waves' bounds */
+  size_t lds_bytes;         /* the scan's dynamic LDS */
+  size_t off_tau, off_eps, off_cnt, off_cand, off_seed; /* byte offsets into the workspace: tau [R] int32, eps [R]
+                               float, cnt [R][nseg] int32, cand [R][nseg][256] int32, seed [R][4096] float */
+  size_t workspace;         /* bytes, = hvae_topk_fused_workspace */
+} hvae_topk_plan;
+int hvae_topk_fused_plan(int64_t R, int64_t N, int64_t D, int64_t K, hvae_topk_plan* out);
 
 /* The 99-negative protocol's negatives, host only, draw for draw numpy's: per test row r, the items
  * neither in row users[r] of the training CSR (row_ptr / col_idx) nor tests[r], ascending ("available",

@@ -31,9 +31,18 @@
 // in ANY association (every summation tree of D terms has depth <= D - 1, so its error is at most
 // (D - 1) 2^-24 sum |u_k e_k| <= D 2^-24 ||u|| ||e||; the term allows twice that for each of s~ and s), and
 // two chains of D / 2 plus one add are such a tree.
+//
+// Host side: tk_plan(R, N, D, K, ab) is a pure function that decides a call once -- the scan, the user mapping,
+// the splits and how the tiles are dealt over them (evenly: no split without a tile), both grids, the sample, the
+// scan's LDS and the workspace as named offsets (hvae_topk_plan, include/hvae.h). hvae_topk_fused_workspace, hvae_topk_fused and the host query hvae_topk_fused_plan all take
+// their numbers from it; kTkWidths is the one list of served widths, behind tk_serves and the one dispatch over D.
+// The product library ships k_topk_scan_lds at every D % 128 == 0 and the global-load k_topk_scan at D = 64 only,
+// always with wave_users = 1. The global-load scan at the other widths, the tile-split mapping (wave_users = 0)
+// and the tau period are A/B switches (TkAb): read from the environment, instantiated and planned in builds with
+// -DHVAE_AB=1 only (tests/ab_checks.py runs them).
 #include <climits>
-
 #include <cstdlib>
+#include <type_traits>
 
 #include "hvae_common.h"
 
@@ -68,6 +77,26 @@ __device__ __forceinline__ float tk_eps(float usq, float emax) {
   return sqrtf(usq) * emax * (0x1p-7f + 0x1p-16f + 4.0f * D * 0x1p-24f) * 1.02f;
 }
 
+// S~^T of tile t (a 32x32 MFMA result): register r of lane half h holds this item
+template <typename T>
+__device__ __forceinline__ T tk_item(T t, int r, int h) {
+  return t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+}
+
+// bitonic network over P2 (a power of two) LDS slots by the block's 256 threads; cas(i, p, up) compares slots
+// i < p and swaps them into the order of an `up` run
+template <typename CAS>
+__device__ __forceinline__ void tk_bitonic(int P2, int tid, CAS cas) {
+  for (int k = 2; k <= P2; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < P2; i += 256) {
+        const int p = i ^ j;
+        if (p > i) cas(i, p, (i & k) == 0);
+      }
+      __syncthreads();
+    }
+}
+
 struct TkScanArgs {
   const float* U;
   int64_t ldu;
@@ -79,7 +108,8 @@ struct TkScanArgs {
   const int64_t* ex_rows_offset;
   int K;
   int splits;
-  int64_t tiles_per_split;
+  int64_t tiles_per_split;  // of the first full_splits splits; the others take one fewer
+  int full_splits;
   int* g_tau;          // [R] ordered-int lower bound t of the K_u-th fp32 score
   float* g_eps;        // [R] eps_u
   float* seed;         // [R][kTkSeed] sampled bf16 scores
@@ -90,6 +120,12 @@ struct TkScanArgs {
                        // from L2, the repeats served by the CU's L1); 0: one user group, waves split the tiles
   int tau_mask;        // other waves' bounds are read every tau_mask + 1 tiles (a power of two minus one)
 };
+
+// first tile of a split: the first full_splits splits take tiles_per_split tiles each and the others one fewer, so
+// the tiles are dealt evenly and no split is empty while there are at least as many tiles as splits
+__device__ __forceinline__ int64_t tk_split_begin(const TkScanArgs& a, int split) {
+  return (int64_t)split * a.tiles_per_split - max(0, split - a.full_splits);
+}
 
 __device__ __forceinline__ int tk_ku(const TkScanArgs& a, int64_t r) {
   int ku = a.K;
@@ -161,7 +197,7 @@ struct TkScorer {
     if (t * 32 + 32 > a.N) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= a.N) s[r] = -INFINITY;
+        if (tk_item(t, r, h) >= a.N) s[r] = -INFINITY;
     }
     return s;
   }
@@ -229,18 +265,10 @@ __global__ void __launch_bounds__(256) k_topk_seed_select(TkScanArgs a, int nsam
   while (P2 < n) P2 <<= 1;
   for (int i = tid; i < P2; i += 256) v[i] = i < n ? a.seed[r * kTkSeed + i] : -INFINITY;
   __syncthreads();
-  for (int k = 2; k <= P2; k <<= 1)  // bitonic, descending
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P2; i += 256) {
-        const int p = i ^ j;
-        if (p > i) {
-          const bool up = (i & k) == 0;
-          const float x = v[i], y = v[p];
-          if ((y > x) == up) { v[i] = y; v[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
+  tk_bitonic(P2, tid, [&](int i, int p, bool up) {  // descending
+    const float x = v[i], y = v[p];
+    if ((y > x) == up) { v[i] = y; v[p] = x; }
+  });
   if (tid == 0) {
     const float kth = ku <= n ? v[ku - 1] : -INFINITY;
     a.g_tau[r] = kth > -INFINITY ? tk_ord(kth - a.g_eps[r]) : INT_MIN;
@@ -298,7 +326,7 @@ struct TkSelect {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
         if (s[r] >= thr) {
-          if (cnt < kTkSegCap) a.cand[seg + cnt] = (int32_t)(t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h);
+          if (cnt < kTkSegCap) a.cand[seg + cnt] = (int32_t)tk_item(t, r, h);
           ++cnt;
         }
     }
@@ -315,8 +343,8 @@ __global__ void __launch_bounds__(256) k_topk_scan(TkScanArgs a) {
                                     : (int64_t)(blockIdx.x / a.splits) * 32 + (lane & 31);
   const bool live = user < a.R;
   const int64_t ntiles = (a.N + 31) / 32;
-  const int64_t t0 = (int64_t)split * a.tiles_per_split;
-  const int64_t t1 = min(ntiles, t0 + a.tiles_per_split);
+  const int64_t t0 = tk_split_begin(a, split);
+  const int64_t t1 = min(ntiles, tk_split_begin(a, split + 1));
   // this wave's tiles: t0 + tw, t0 + tw + ts, ... (every tile of the split with wave_users)
   const int tw = a.wave_users ? 0 : w, ts = a.wave_users ? 1 : 4;
   const int64_t nw = t1 > t0 + tw ? (t1 - t0 - tw + ts - 1) / ts : 0;
@@ -351,15 +379,11 @@ __global__ void __launch_bounds__(256) k_topk_scan(TkScanArgs a) {
 // + 8 KiB exchange + 2 x 32 heaps of 63 floats (16 KiB set aside) = 152 KiB.
 constexpr int tkl_kh(int64_t D) { return D >= 1024 ? 2 : 1; }          // D-halves (waves per user group)
 constexpr int tkl_block_users(int64_t D) { return 128 / tkl_kh(D); }  // users per block
-template <int D>
-constexpr int tkl_ns() { return D >= 768 ? 2 : 3; }
-template <int D>
-constexpr int tkl_heap() { return D >= 768 ? 64 : 128; }
-template <int D>
-constexpr int tkl_xchg_bytes() { return tkl_kh(D) == 2 ? (4 / tkl_kh(D)) * 4096 : 0; }
-template <int D>
-constexpr int tkl_lds_bytes() {
-  return tkl_ns<D>() * ((D / 128) * 8192) + tkl_xchg_bytes<D>() + tkl_block_users(D) * tkl_heap<D>() * 4;
+constexpr int tkl_ns(int64_t D) { return D >= 768 ? 2 : 3; }
+constexpr int tkl_heap(int64_t D) { return D >= 768 ? 64 : 128; }
+constexpr int tkl_xchg_bytes(int64_t D) { return tkl_kh(D) == 2 ? (4 / tkl_kh(D)) * 4096 : 0; }
+constexpr int64_t tkl_lds_bytes(int64_t D) {  // the plan's too, hence functions of a runtime D
+  return tkl_ns(D) * ((D / 128) * 8192) + tkl_xchg_bytes(D) + tkl_block_users(D) * tkl_heap(D) * 4;
 }
 
 __device__ __forceinline__ uint32_t tk_lds_addr(const void* p) {
@@ -373,13 +397,13 @@ __device__ __forceinline__ void tk_wait_vmcnt() {
 
 template <int D>
 __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
-  constexpr int NSEG = D / 128, TB = NSEG * 8192, PW = NSEG * 8 / 4, NS = tkl_ns<D>();
+  constexpr int NSEG = D / 128, TB = NSEG * 8192, PW = NSEG * 8 / 4, NS = tkl_ns(D);
   constexpr int KH = tkl_kh(D), KS = D / 16 / KH;  // a wave's k-steps: its D-half with KH = 2
-  constexpr int HC = tkl_heap<D>() - 1;  // heap capacity = stride: odd, so the 32 users' slots fall on 32 banks
-  static_assert(D % 128 == 0 && tkl_lds_bytes<D>() <= 160 * 1024, "k_topk_scan_lds shape");
+  constexpr int HC = tkl_heap(D) - 1;  // heap capacity = stride: odd, so the 32 users' slots fall on 32 banks
+  static_assert(D % 128 == 0 && tkl_lds_bytes(D) <= 160 * 1024, "k_topk_scan_lds shape");
   static_assert(KH == 1 || KS / 2 == PW, "the D-split chain issues one DMA piece every second k-step");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  float* heaps = reinterpret_cast<float*>(lds + NS * TB + tkl_xchg_bytes<D>());
+  float* heaps = reinterpret_cast<float*>(lds + NS * TB + tkl_xchg_bytes(D));
   const int tid = threadIdx.x, lane = tid & 63, h = lane >> 5, col = lane & 31;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ug = w / KH, kh = w % KH;  // the wave's user group and D-half (KH = 1: ug = w, kh = 0)
@@ -388,8 +412,8 @@ __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
   const bool live = user < a.R;
   const bool sel_live = live && kh == 0;  // the wave that selects for the group
   const int64_t ntiles = (a.N + 31) / 32;
-  const int64_t t0 = (int64_t)split * a.tiles_per_split;
-  const int64_t t1 = min(ntiles, t0 + a.tiles_per_split);
+  const int64_t t0 = tk_split_begin(a, split);
+  const int64_t t1 = min(ntiles, tk_split_begin(a, split + 1));
   const int64_t nt = t1 > t0 ? t1 - t0 : 0;
   const float emax = *a.e_maxnorm;  // before any LDS-DMA is in flight
 
@@ -524,7 +548,7 @@ __global__ void __launch_bounds__(256) k_topk_scan_lds(TkScanArgs a) {
     if (t * 32 + 32 > a.N) {
 #pragma unroll
       for (int r = 0; r < 16; ++r)
-        if (t * 32 + (r & 3) + 8 * (r >> 2) + 4 * h >= a.N) s[r] = -INFINITY;
+        if (tk_item(t, r, h) >= a.N) s[r] = -INFINITY;
     }
     if (kh == 0) sel.consume(a, s, t, j);
   }
@@ -594,18 +618,10 @@ __global__ void __launch_bounds__(256) k_topk_select(TkSelArgs a) {
   while (P2s < nseen) P2s <<= 1;
   for (int i = tid; i < P2s; i += 256) seen[i] = i < nseen ? a.ex_col[a.ex_row_ptr[m] + i] : INT_MAX;
   __syncthreads();
-  for (int k = 2; k <= P2s; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P2s; i += 256) {
-        const int p = i ^ j;
-        if (p > i) {
-          const bool up = (i & k) == 0;
-          const int x = seen[i], y = seen[p];
-          if ((x > y) == up) { seen[i] = y; seen[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
+  tk_bitonic(P2s, tid, [&](int i, int p, bool up) {
+    const int x = seen[i], y = seen[p];
+    if ((x > y) == up) { seen[i] = y; seen[p] = x; }
+  });
   // gather the candidates
   for (int sgi = 0; sgi < a.nseg; ++sgi) {
     const int o = s_off[sgi], n = s_off[sgi + 1] - o;
@@ -652,19 +668,11 @@ __global__ void __launch_bounds__(256) k_topk_select(TkSelArgs a) {
   for (int i = C + tid; i < P2; i += 256) { ss[i] = -INFINITY; si[i] = -1; }
   __syncthreads();
   // bitonic sort, "before" first
-  for (int k = 2; k <= P2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < P2; i += 256) {
-        const int p = i ^ j;
-        if (p > i) {
-          const bool up = (i & k) == 0;
-          const float x = ss[i], y = ss[p];
-          const int xi = si[i], yi = si[p];
-          if (tk_before(y, yi, x, xi) == up) { ss[i] = y; si[i] = yi; ss[p] = x; si[p] = xi; }
-        }
-      }
-      __syncthreads();
-    }
+  tk_bitonic(P2, tid, [&](int i, int p, bool up) {
+    const float x = ss[i], y = ss[p];
+    const int xi = si[i], yi = si[p];
+    if (tk_before(y, yi, x, xi) == up) { ss[i] = y; si[i] = yi; ss[p] = x; si[p] = xi; }
+  });
   // fewer than K finite candidates (seen items ate the shortlist): the exact path decides
   if (tid == 0) a.flag[r] = !(ss[a.K - 1] > -INFINITY);
   for (int i = tid; i < a.K; i += 256) {
@@ -673,33 +681,103 @@ __global__ void __launch_bounds__(256) k_topk_select(TkSelArgs a) {
   }
 }
 
-static int tk_lds_scan(int64_t D) {  // HVAE_TOPK_LDS=0 keeps the global-load scan (A/B)
-  const char* v = ab_getenv("HVAE_TOPK_LDS");
-  return D % 128 == 0 && ((v && *v) ? (atoi(v) != 0) : 1);
+// ---- host: one plan per call ----
+
+// A/B overrides of the plan, in the environment of builds with -DHVAE_AB=1 only (read at every plan); the default is
+// the product's, and the product build has no other
+struct TkAb {
+  int lds_scan = 1;    // HVAE_TOPK_LDS=0: the global-load scan where D % 128 == 0 too
+  int wave_users = 1;  // HVAE_TOPK_WAVE_USERS=0: the global-load scan's tile-split mapping
+  int tau_period = 8;  // HVAE_TK_TAU_PERIOD: tiles between reads of the other waves' bounds (a power of two, else 8)
+};
+static TkAb tk_ab() {
+  TkAb ab;
+#if HVAE_AB
+  auto env = [](const char* name, int dflt) {
+    const char* v = getenv(name);
+    return (v && *v) ? atoi(v) : dflt;
+  };
+  ab.lds_scan = env("HVAE_TOPK_LDS", ab.lds_scan) != 0;
+  ab.wave_users = env("HVAE_TOPK_WAVE_USERS", ab.wave_users) != 0;
+  ab.tau_period = env("HVAE_TK_TAU_PERIOD", ab.tau_period);
+#endif
+  return ab;
 }
 
-static int tk_wave_users() {  // HVAE_TOPK_WAVE_USERS=0 selects the tile-split mapping (A/B)
-  const char* v = ab_getenv("HVAE_TOPK_WAVE_USERS");
-  return (v && *v) ? (atoi(v) != 0) : 1;
+// The served widths: tk_serves and tk_dispatch both go by this list, and D / 64 (k_topk_select), the seed's k
+// ranges and the scan's form follow from D in hvae_topk_fused's dispatched launch.
+constexpr int kTkWidths[] = {64, 128, 256, 384, 512, 768, 1024};
+constexpr int kTkNumWidths = sizeof(kTkWidths) / sizeof(kTkWidths[0]);
+constexpr bool tk_serves(int64_t D, int64_t K) {
+  for (int w : kTkWidths)
+    if (D == w) return K <= kTkHeap;
+  return false;
+}
+// f(std::integral_constant<int, D>) for the served D
+template <int I = 0, typename F>
+static int tk_dispatch(int64_t D, F&& f) {
+  if constexpr (I == kTkNumWidths) {
+    HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_topk_fused: no kernel for D = %lld", (long long)D);
+  } else {
+    return D == kTkWidths[I] ? f(std::integral_constant<int, kTkWidths[I]>{}) : tk_dispatch<I + 1>(D, f);
+  }
 }
 
 // a split's bf16 slice of E must stay below 2^31 bytes (the LDS scan's buffer resource extent is 32-bit): with
 // cdiv(bytes, 2^30) splits a slice is at most 2^30 bytes + one tile (64 KiB at d = 1024's 2048 B per row)
 constexpr int64_t kTkSplitBytes = (int64_t)1 << 30;
 
-// users per scan block; the workspace's nseg, tk_splits and the launch's block count all go by it
-static int tk_block_users(int64_t D, int lds_scan, int wave_users) {
-  return lds_scan ? tkl_block_users(D) : wave_users ? 128 : 32;
-}
+struct TkRefusal {
+  int code;         // HVAE_OK: the plan stands
+  const char* why;
+};
 
-static int tk_splits(int64_t R, int64_t N, int64_t D, int wave_users, int block_users) {
-  const int64_t groups = std::max<int64_t>(1, cdiv(R, block_users));  // R = 0: a workspace query
+// Everything a call needs, decided once. Every field is filled in whatever the verdict (an unserved width is sized
+// as the scan its D would get: hvae_topk_fused_workspace answers for those too); the verdict says whether
+// hvae_topk_fused runs it.
+static TkRefusal tk_plan(int64_t R, int64_t N, int64_t D, int64_t K, const TkAb& ab, hvae_topk_plan* p) {
+  bool lds = D % 128 == 0;
+  int wu = 1;
+  if constexpr (HVAE_AB != 0) {  // the product plans the LDS scan wherever it exists, and one mapping
+    lds = lds && ab.lds_scan != 0;
+    if (!lds) wu = ab.wave_users != 0;
+  }
+  p->scan = !lds ? HVAE_TOPK_SCAN_GLOBAL : tkl_kh(D) == 2 ? HVAE_TOPK_SCAN_LDS_KH2 : HVAE_TOPK_SCAN_LDS;
+  p->wave_users = wu;
+  p->block_users = lds ? tkl_block_users(D) : wu ? 128 : 32;
+  const int64_t groups = std::max<int64_t>(1, cdiv(R, p->block_users));  // R = 0: a workspace query
   const int64_t tiles = cdiv(N, 32);
   int64_t s = std::max<int64_t>(1, cdiv(256, groups));  // ~256 blocks (one per CU: 128 KiB of heaps each)
-  s = std::min<int64_t>(s, std::max<int64_t>(1, tiles / (wave_users ? 4 : 16)));  // >= 4 tiles per wave
+  s = std::min<int64_t>(s, std::max<int64_t>(1, tiles / (wu ? 4 : 16)));  // >= 4 tiles per wave
   s = std::max<int64_t>(s, cdiv(tiles * 32 * D * 2, kTkSplitBytes));  // large E: enough splits for the extent
-  s = std::min<int64_t>(s, wave_users ? 512 : 128);  // nseg <= 1024
-  return (int)s;
+  s = std::min<int64_t>(s, wu ? 512 : 128);  // nseg <= 1024
+  p->splits = (int)s;
+  p->tiles_per_split = cdiv(tiles, s);
+  p->full_splits = (int)(tiles - s * (p->tiles_per_split - 1));  // the other splits take one tile fewer
+  p->nseg = p->splits * (wu ? 2 : 8);
+  p->blocks = cdiv(R, p->block_users) * s;
+  p->seed_blocks = cdiv(R, 32);  // the seed pass: one block per 32 users
+  p->nsample = (int)std::min<int64_t>(tiles, kTkSeedTiles);
+  p->stride = std::max<int64_t>(1, tiles / std::max(1, p->nsample));
+  p->tau_period = (ab.tau_period >= 1 && (ab.tau_period & (ab.tau_period - 1)) == 0) ? ab.tau_period : 8;
+  p->lds_bytes = lds ? (size_t)tkl_lds_bytes(D) : (size_t)4 * 32 * (kTkHeap + kTkHeapPad) * 4;
+  // workspace: 256 B | tau [R] | eps [R] | cnt [R][nseg] | cand [R][nseg][kTkSegCap] | seed [R][kTkSeed]
+  p->off_tau = 256;
+  p->off_eps = p->off_tau + (size_t)R * 4;
+  p->off_cnt = p->off_eps + (size_t)R * 4;
+  p->off_cand = p->off_cnt + (size_t)R * p->nseg * 4;
+  p->off_seed = p->off_cand + (size_t)R * p->nseg * kTkSegCap * 4;
+  p->workspace = p->off_seed + (size_t)R * kTkSeed * 4;
+
+  if (!tk_serves(D, K)) return {HVAE_ERR_UNSUPPORTED, "D must be 64, 128, 256, 384, 512, 768 or 1024, K <= 256"};
+  if (R < 0 || N <= 0 || K <= 0) return {HVAE_ERR_ARG, "bad args"};
+  // d = 1024 has the D-split LDS scan only: the global-load scan (A/B: HVAE_TOPK_LDS=0) would keep all of u in
+  // registers and spill, so it is not instantiated
+  if (!lds && tkl_kh(D) == 2) return {HVAE_ERR_UNSUPPORTED, "D = 1024 has no global-load scan"};
+  if (K > N || N >= INT32_MAX) return {HVAE_ERR_ARG, "bad args"};
+  if (lds && p->tiles_per_split * 32 * D * 2 >= ((int64_t)1 << 31))
+    return {HVAE_ERR_ARG, "a split of E exceeds 2^31 bytes"};
+  return {HVAE_OK, nullptr};
 }
 
 }  // namespace hvae
@@ -707,109 +785,73 @@ static int tk_splits(int64_t R, int64_t N, int64_t D, int wave_users, int block_
 using namespace hvae;
 
 extern "C" size_t hvae_topk_fused_workspace(int64_t R, int64_t N, int64_t D, int64_t K) {
-  const int lds_scan = tk_lds_scan(D);
-  const int wu = lds_scan ? 1 : tk_wave_users();
-  const int s = tk_splits(R, N, D, wu, tk_block_users(D, lds_scan, wu));
-  const size_t nseg = (size_t)s * (wu ? 2 : 8);
-  return 256 + (size_t)R * 8 + (size_t)R * nseg * 4 + (size_t)R * nseg * kTkSegCap * 4 + (size_t)R * kTkSeed * 4;
+  hvae_topk_plan p;
+  tk_plan(R, N, D, K, tk_ab(), &p);
+  return p.workspace;
 }
 
-// HVAE_TK_TAU_PERIOD (A/B, read at every call; a power of two): tiles between reads of the other waves' bounds
-static int tk_tau_mask() {
-  const char* e = ab_getenv("HVAE_TK_TAU_PERIOD");
-  int p = e ? std::atoi(e) : 8;
-  if (p < 1 || (p & (p - 1)) != 0) p = 8;
-  return p - 1;
+extern "C" int hvae_topk_fused_plan(int64_t R, int64_t N, int64_t D, int64_t K, hvae_topk_plan* out) {
+  HVAE_REQUIRE(out, "hvae_topk_fused_plan: null out");
+  const TkRefusal no = tk_plan(R, N, D, K, tk_ab(), out);
+  if (no.code != HVAE_OK) HVAE_FAIL(no.code, "hvae_topk_fused_plan: %s", no.why);
+  return HVAE_OK;
 }
 
 extern "C" int hvae_topk_fused(const float* U, int64_t ldu, const void* E_bf16, const float* E32,
                                const float* e32_maxnorm, int64_t N, int64_t D, const hvae_csr_batch* exclude,
                                int64_t R, int64_t K, int32_t* idx, float* val, int32_t* flag, void* ws,
                                size_t ws_bytes, void* stream) {
-  HVAE_REQUIRE(R >= 0 && ldu >= D && K > 0 && K <= kTkHeap && K <= N && N < INT32_MAX, "hvae_topk_fused: bad args");
-  HVAE_REQUIRE(D == 64 || D == 128 || D == 256 || D == 384 || D == 512 || D == 768 || D == 1024,
-               "hvae_topk_fused: D must be 64, 128, 256, 384, 512, 768 or 1024");
+  hvae_topk_plan pl;
+  const TkRefusal no = tk_plan(R, N, D, K, tk_ab(), &pl);
+  if (no.code != HVAE_OK) HVAE_FAIL(no.code, "hvae_topk_fused: %s", no.why);
+  HVAE_REQUIRE(ldu >= D, "hvae_topk_fused: bad args");
   if (R == 0) return HVAE_OK;  // an empty batch: its (empty) output tensors may have null data pointers
   HVAE_REQUIRE(U && E_bf16 && E32 && e32_maxnorm && idx && flag, "hvae_topk_fused: null pointer");
-  HVAE_REQUIRE(ws && ws_bytes >= hvae_topk_fused_workspace(R, N, D, K), "hvae_topk_fused: workspace too small");
+  HVAE_REQUIRE(ws && ws_bytes >= pl.workspace, "hvae_topk_fused: workspace too small");
   if (exclude)
     HVAE_REQUIRE(exclude->row_ptr && exclude->col_idx && exclude->nb == R, "hvae_topk_fused: bad exclude");
   hipStream_t st = as_stream(stream);
-  const bool lds_scan = tk_lds_scan(D);
-  // d = 1024 has the D-split LDS scan only: the global-load scan (A/B: HVAE_TOPK_LDS=0) would keep all of u in
-  // registers and spill, so it is not instantiated
-  if (D == 1024 && !lds_scan) HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_topk_fused: D = 1024 has no global-load scan");
-  const int wu = lds_scan ? 1 : tk_wave_users();
-  const int block_users = tk_block_users(D, lds_scan, wu);
-  const int splits = tk_splits(R, N, D, wu, block_users);
-  const int nseg = splits * (wu ? 2 : 8);
-  HVAE_REQUIRE(!lds_scan || cdiv(cdiv(N, 32), splits) * 32 * D * 2 < ((int64_t)1 << 31),
-               "hvae_topk_fused: a split of E exceeds 2^31 bytes");
-  unsigned char* p = static_cast<unsigned char*>(ws);
-  int* g_tau = reinterpret_cast<int*>(p + 256);
-  float* g_eps = reinterpret_cast<float*>(g_tau + R);
-  int32_t* cnt = reinterpret_cast<int32_t*>(g_eps + R);
-  int32_t* cand = cnt + (size_t)R * nseg;
-  float* seed = reinterpret_cast<float*>(cand + (size_t)R * nseg * kTkSegCap);
-  HVAE_HIP(hipMemsetAsync(cnt, 0, (size_t)R * nseg * 4, st));
+  unsigned char* w = static_cast<unsigned char*>(ws);
+  int32_t* cnt = reinterpret_cast<int32_t*>(w + pl.off_cnt);
+  int32_t* cand = reinterpret_cast<int32_t*>(w + pl.off_cand);
+  HVAE_HIP(hipMemsetAsync(cnt, 0, pl.off_cand - pl.off_cnt, st));
   HVAE_HIP(hipMemsetAsync(flag, 0, (size_t)R * 4, st));
-  TkScanArgs sa{U, ldu, static_cast<const bf16_t*>(E_bf16), e32_maxnorm, R, N,
-                exclude ? exclude->row_ptr : nullptr, exclude ? exclude->rows : nullptr,
-                exclude ? exclude->rows_offset : nullptr, (int)K, splits, cdiv(cdiv(N, 32), splits), g_tau, g_eps,
-                seed, cand, cnt, nseg, wu, tk_tau_mask()};
-  const int64_t ntiles = cdiv(N, 32);
-  const int nsample = (int)std::min<int64_t>(ntiles, kTkSeedTiles);
-  const int64_t stride = std::max<int64_t>(1, ntiles / nsample);
-  const unsigned groups = (unsigned)cdiv(R, 32);  // the seed pass: one block per 32 users
-  const unsigned blocks = (unsigned)(cdiv(R, block_users) * splits);
-  const size_t lds = (size_t)4 * 32 * (kTkHeap + kTkHeapPad) * 4;
-#define TK_SCAN_LDS(DD)                                                                                 \
-  {                                                                                                       \
-    constexpr int DL = DD % 128 == 0 ? DD : 128;                                                          \
-    HVAE_HIP(hipFuncSetAttribute((const void*)k_topk_scan_lds<DL>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 tkl_lds_bytes<DL>()));                                                   \
-    k_topk_scan_lds<DL><<<blocks, 256, tkl_lds_bytes<DL>(), st>>>(sa);                                   \
-  }
-  switch (D) {
-#define TK_CASE(DD)                                                                                       \
-  case DD:                                                                                                \
-    k_topk_seed<DD><<<groups, 256, 0, st>>>(sa, stride, nsample);                                        \
-    HVAE_LAUNCH_CHECK("k_topk_seed");                                                                     \
-    k_topk_seed_select<<<(unsigned)R, 256, 0, st>>>(sa, nsample);                                         \
-    HVAE_LAUNCH_CHECK("k_topk_seed_select");                                                              \
-    if (DD % 128 == 0 && lds_scan) {                                                                      \
-      TK_SCAN_LDS(DD)                                                                                     \
-    } else {                                                                                              \
-      HVAE_HIP(hipFuncSetAttribute((const void*)k_topk_scan<DD>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                   (int)lds));                                                            \
-      k_topk_scan<DD><<<blocks, 256, lds, st>>>(sa);                                                      \
-    }                                                                                                     \
-    HVAE_LAUNCH_CHECK("k_topk_scan");                                                                     \
-    break;
-    TK_CASE(64) TK_CASE(128) TK_CASE(256) TK_CASE(384) TK_CASE(512) TK_CASE(768)
-#undef TK_CASE
-    case 1024:  // the D-split seed and LDS scan
-      k_topk_seed_split<1024><<<groups, 256, 0, st>>>(sa, stride, nsample);
-      HVAE_LAUNCH_CHECK("k_topk_seed_split");
-      k_topk_seed_select<<<(unsigned)R, 256, 0, st>>>(sa, nsample);
-      HVAE_LAUNCH_CHECK("k_topk_seed_select");
-      TK_SCAN_LDS(1024)
-      HVAE_LAUNCH_CHECK("k_topk_scan");
-      break;
-#undef TK_SCAN_LDS
-  }
-  TkSelArgs la{U, ldu, E32, R, N, D, exclude ? exclude->row_ptr : nullptr, exclude ? exclude->col_idx : nullptr,
-               exclude ? exclude->rows : nullptr, exclude ? exclude->rows_offset : nullptr, (int)K, cand, cnt, nseg,
-               idx, val, flag};
-  switch (D) {
-    case 64: k_topk_select<1><<<(unsigned)R, 256, 0, st>>>(la); break;
-    case 128: k_topk_select<2><<<(unsigned)R, 256, 0, st>>>(la); break;
-    case 256: k_topk_select<4><<<(unsigned)R, 256, 0, st>>>(la); break;
-    case 384: k_topk_select<6><<<(unsigned)R, 256, 0, st>>>(la); break;
-    case 512: k_topk_select<8><<<(unsigned)R, 256, 0, st>>>(la); break;
-    case 768: k_topk_select<12><<<(unsigned)R, 256, 0, st>>>(la); break;
-    default: k_topk_select<16><<<(unsigned)R, 256, 0, st>>>(la); break;
-  }
-  HVAE_LAUNCH_CHECK("k_topk_select");
-  return HVAE_OK;
+  const TkScanArgs sa{U, ldu, static_cast<const bf16_t*>(E_bf16), e32_maxnorm, R, N,
+                      exclude ? exclude->row_ptr : nullptr, exclude ? exclude->rows : nullptr,
+                      exclude ? exclude->rows_offset : nullptr, (int)K, pl.splits, pl.tiles_per_split,
+                      pl.full_splits,
+                      reinterpret_cast<int*>(w + pl.off_tau), reinterpret_cast<float*>(w + pl.off_eps),
+                      reinterpret_cast<float*>(w + pl.off_seed), cand, cnt, pl.nseg, pl.wave_users,
+                      pl.tau_period - 1};
+  const TkSelArgs la{U, ldu, E32, R, N, D, exclude ? exclude->row_ptr : nullptr,
+                     exclude ? exclude->col_idx : nullptr, exclude ? exclude->rows : nullptr,
+                     exclude ? exclude->rows_offset : nullptr, (int)K, cand, cnt, pl.nseg, idx, val, flag};
+  return tk_dispatch(D, [&](auto width) -> int {
+    constexpr int DD = decltype(width)::value;
+    const dim3 seed_grid((unsigned)pl.seed_blocks);
+    if constexpr (tkl_kh(DD) == 2) k_topk_seed_split<DD><<<seed_grid, 256, 0, st>>>(sa, pl.stride, pl.nsample);
+    else k_topk_seed<DD><<<seed_grid, 256, 0, st>>>(sa, pl.stride, pl.nsample);
+    HVAE_LAUNCH_CHECK("k_topk_seed");
+    k_topk_seed_select<<<(unsigned)R, 256, 0, st>>>(sa, pl.nsample);
+    HVAE_LAUNCH_CHECK("k_topk_seed_select");
+    // the global-load scan where the LDS scan exists is an A/B arm: the product neither plans nor holds it
+    constexpr bool has_global = DD % 128 != 0 || (HVAE_AB != 0 && tkl_kh(DD) == 1);
+    if (pl.scan != HVAE_TOPK_SCAN_GLOBAL) {
+      if constexpr (DD % 128 == 0) {
+        HVAE_HIP(hipFuncSetAttribute((const void*)k_topk_scan_lds<DD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)pl.lds_bytes));
+        k_topk_scan_lds<DD><<<(unsigned)pl.blocks, 256, pl.lds_bytes, st>>>(sa);
+      }
+    } else if constexpr (has_global) {
+      HVAE_HIP(hipFuncSetAttribute((const void*)k_topk_scan<DD>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)pl.lds_bytes));
+      k_topk_scan<DD><<<(unsigned)pl.blocks, 256, pl.lds_bytes, st>>>(sa);
+    } else {
+      HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_topk_fused: this build has no global-load scan at D = %d", DD);
+    }
+    HVAE_LAUNCH_CHECK("k_topk_scan");
+    k_topk_select<DD / 64><<<(unsigned)R, 256, 0, st>>>(la);
+    HVAE_LAUNCH_CHECK("k_topk_select");
+    return HVAE_OK;
+  });
 }

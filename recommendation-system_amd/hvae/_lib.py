@@ -89,6 +89,19 @@ DEC_SWEEPS = ("none", "bf16_v1", "bf16_v2", "bf16_v3", "bf16_v4", "bf16_v5", "bf
               "fp8_v4", "fp8_v5", "f32")
 
 
+class TopkPlan(C.Structure):  # hvae_topk_plan
+    _fields_ = [("scan", cint), ("wave_users", cint), ("block_users", cint), ("splits", cint),
+                ("tiles_per_split", i64), ("full_splits", cint), ("nseg", cint), ("blocks", i64),
+                ("seed_blocks", i64), ("nsample", cint),
+                ("stride", i64), ("tau_period", cint), ("lds_bytes", sz), ("off_tau", sz), ("off_eps", sz),
+                ("off_cnt", sz), ("off_cand", sz), ("off_seed", sz), ("workspace", sz)]
+
+
+# include/hvae.h HVAE_TOPK_SCAN_*, by value
+TOPK_SCANS = ("global", "lds", "lds_kh2")
+HVAE_ERR_UNSUPPORTED = -3
+
+
 class MlpRows(C.Structure):  # hvae_mlp_rows
     _fields_ = [
         ("nb", i64), ("H", i64), ("L", i64), ("D", i64),
@@ -204,6 +217,7 @@ SIGNATURES = {
     "hvae_topk_fused_workspace": (sz, [i64, i64, i64, i64]),
     "hvae_topk_fused": (cint, [vp, i64, vp, vp, vp, i64, i64, P(CsrBatch), i64, i64, vp, vp, vp, vp, sz,
                                vp]),
+    "hvae_topk_fused_plan": (cint, [i64, i64, i64, i64, P(TopkPlan)]),
     "hvae_csc_col_stats": (cint, [vp, vp, vp, i64, vp, vp, vp]),
     "hvae_knn_workspace": (sz, [i64, i64]),
     "hvae_knn_user_weights": (cint, [P(CsrBatch), vp, vp, vp, vp, i64, vp, sz, vp]),

@@ -474,6 +474,13 @@ def topk(scores: torch.Tensor, k: int, exclude: Csr | None = None):
     return idx, val
 
 
+def topk_fused_supported(d: int, k: int) -> bool:
+    """Whether hvae_topk_fused serves embedding width d and k results per row: what its plan (hvae_topk_fused_plan, a
+    host query) answers, asked for k items so that nothing but the pair (d, k) can be refused as unsupported."""
+    p = _lib.TopkPlan()
+    return lib().hvae_topk_fused_plan(0, max(k, 1), d, k, C.byref(p)) != _lib.HVAE_ERR_UNSUPPORTED
+
+
 def topk_fused(U: torch.Tensor, E_img: "DecoderImage", E32: torch.Tensor, e32_maxnorm: torch.Tensor, k: int,
                exclude: Csr | None = None, with_flags: bool = False):
     """Exact top-k of U E32^T per row (score desc, ties -> larger index first; `exclude`'s items of each row

@@ -182,11 +182,11 @@ class HybridVAE(nn.Module):
 
     def topk_scores(self, u: torch.Tensor, k: int, exclude: "ops.Csr | None" = None):
         """Exact top-k of u E^T per row (exclude: CSR rows of items left out), fused where hvae_topk_fused covers
-        the shape (k <= 256, d one of 64, 128, 256, 384, 512, 768, 1024: every bf16 width the trainer serves), else
-        through the fp32 score matrix + hvae_topk (both on the GPU)."""
+        the shape (ops.topk_fused_supported: k <= 256 at every bf16 width the trainer serves), else through the fp32
+        score matrix + hvae_topk (both on the GPU)."""
         E = self.item_embeddings.detach()
         d = E.shape[1]
-        if k <= 256 and d in (64, 128, 256, 384, 512, 768, 1024) and k <= E.shape[0]:
+        if ops.topk_fused_supported(d, k) and k <= E.shape[0]:
             # the bf16 image and max||E|| are cached for a frozen E; the key carries the tensor's version, which
             # load_state_dict / copy_ bump. A trainable E is written in place by libhvae's Adam (no version bump),
             # so its image is rebuilt on every call

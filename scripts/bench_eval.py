@@ -76,7 +76,10 @@ def main():
         S = ops.gemm(u, model.item_embeddings.t())
         return ops.topk(S, k, exclude=c)
 
+    import ctypes
     import os
+
+    from hvae import _lib
 
     def run_fused_global(rows):  # A/B: the scan reading E fragments straight from global memory
         os.environ["HVAE_TOPK_LDS"] = "0"
@@ -85,12 +88,28 @@ def main():
         finally:
             os.environ.pop("HVAE_TOPK_LDS")
 
-    # d = 1024 has no global-load scan (hvae_topk.hip: it would spill)
-    arms = [("topk_fused", run_fused)] + \
-        ([] if w["d"] == 1024 else [("topk_fused_global_scan", run_fused_global)]) + \
+    def global_scan_planned():
+        """Does the loaded library, under HVAE_TOPK_LDS=0, plan the global-load scan for this workload? Only the A/B
+        build reads the switch, and d = 1024 has no global-load scan (hvae_topk.hip: it would spill)."""
+        p, p0 = _lib.TopkPlan(), _lib.TopkPlan()
+        _lib.lib().hvae_topk_fused_plan(B, w["items"], w["d"], k, ctypes.byref(p0))  # what topk_fused times
+        os.environ["HVAE_TOPK_LDS"] = "0"
+        try:
+            rc = _lib.lib().hvae_topk_fused_plan(B, w["items"], w["d"], k, ctypes.byref(p))
+        finally:
+            os.environ.pop("HVAE_TOPK_LDS")
+        return rc == _lib.HVAE_OK and _lib.TOPK_SCANS[p.scan] == "global" and p0.scan != p.scan
+
+    arms = [("topk_fused", run_fused), ("topk_fused_global_scan", run_fused_global)] + \
         ([] if args.skip_matrix else [("topk_matrix", run_matrix)])
     if args.probes:
         arms = [a for a in arms if a[0] in args.probes]
+    if any(a[0] == "topk_fused_global_scan" for a in arms) and not global_scan_planned():
+        arms = [a for a in arms if a[0] != "topk_fused_global_scan"]
+        print(json.dumps({"workload": args.workload, "probe": "topk_fused_global_scan", "skipped":
+                          "the loaded library plans no global-load scan here: the product library ignores "
+                          "HVAE_TOPK_LDS (use the A/B build, HVAE_LIB=build_var/libhvae_ab.so), and d = 1024 has "
+                          "no global-load scan"}), flush=True)
     res = {}
     rows = [batch_rows() for _ in range(args.reps)]  # the same batches for every arm
     for name, fn in arms:

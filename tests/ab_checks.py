@@ -4,7 +4,9 @@ The product libhvae.so runs one sweep per (dtype, d) and ignores the environment
 versions 2, 3 and 4 at d = 768 beside version 5, version 6 (96 users per E tile), the d = 384 version 5
 (k_dec5w_bf16), the fp8 sweep with version 4's structure (k_dec4_f8) and the D-split ring beside the fp8 version 5
 (k_dec5_f8) -- live in recommendation-system_amd/csrc/ab/ and build only with -DHVAE_AB=1
-(`make -C recommendation-system_amd lib-ab` -> build_var/libhvae_ab.so), where HVAE_DEC_* select them at plan time. tests/test_gpu_ab_variant.py runs this file
+(`make -C recommendation-system_amd lib-ab` -> build_var/libhvae_ab.so), where HVAE_DEC_* select them at plan time.
+The same build holds the fused top-K's A/B arms (HVAE_TOPK_LDS, HVAE_TOPK_WAVE_USERS, HVAE_TK_TAU_PERIOD: the
+global-load scan at the LDS-served widths and its tile-split mapping). tests/test_gpu_ab_variant.py runs this file
 in a subprocess with HVAE_LIB pointing at that build, so the variants keep their parity checks without being
 shipped.
 """
@@ -175,6 +177,41 @@ def test_rowgrad_sorted_plan_equals_atomic_plan(ops, dev, nb, N, lam, hot, monke
         assert torch.equal(x, y)
     assert a[9] == 0 and a[10] == 0
     np.testing.assert_array_equal(a[2].cpu().numpy(), np.unique(X.indices))
+
+
+@pytest.mark.parametrize("R,N", [(33, 4097), (130, 777)])
+@pytest.mark.parametrize("D", [128, 768])
+def test_topk_fused_scans_and_mappings_agree(ops, dev, D, R, N, monkeypatch):
+    """The fused top-K's A/B arms -- the global-load scan where the product runs the LDS scan (HVAE_TOPK_LDS=0), its
+    tile-split mapping (HVAE_TOPK_WAVE_USERS=0) and a read of the other waves' bounds at every tile
+    (HVAE_TK_TAU_PERIOD=1) -- against float64 (tests/test_gpu_topk.py's check and tolerance), each named by the plan
+    query before it runs. The final ranking is an exact fp32 rescore of the candidates in a fixed order, so the path
+    the candidates took must not show: idx and val are bitwise the default setting's."""
+    import ctypes as C
+    from hvae._lib import TOPK_SCANS, TopkPlan, check, lib
+    from test_gpu_topk import _case, _check
+    k = 10
+    U, E, Ud, Ed, img, emax = _case(dev, R, N, D, seed=N + D)
+    settings = [({}, ("lds", 1, 128, 8)),
+                ({"HVAE_TOPK_LDS": "0"}, ("global", 1, 128, 8)),
+                ({"HVAE_TOPK_LDS": "0", "HVAE_TOPK_WAVE_USERS": "0"}, ("global", 0, 32, 8)),
+                ({"HVAE_TK_TAU_PERIOD": "1"}, ("lds", 1, 128, 1))]
+    out = []
+    for env, want in settings:
+        for name in ("HVAE_TOPK_LDS", "HVAE_TOPK_WAVE_USERS", "HVAE_TK_TAU_PERIOD"):
+            monkeypatch.delenv(name, raising=False)
+        for name, v in env.items():
+            monkeypatch.setenv(name, v)
+        p = TopkPlan()
+        check(lib().hvae_topk_fused_plan(R, N, D, k, C.byref(p)), "hvae_topk_fused_plan")
+        assert (TOPK_SCANS[p.scan], p.wave_users, p.block_users, p.tau_period) == want, env
+        assert p.nseg == p.splits * (2 if p.wave_users else 8)
+        idx, val, flag = ops.topk_fused(Ud, img, Ed, emax, k, with_flags=True)
+        assert int(flag.sum()) == 0, env
+        _check(idx, val, U, E, k)
+        out.append((idx, val))
+    for (idx, val), (env, _) in zip(out[1:], settings[1:]):
+        assert torch.equal(idx, out[0][0]) and torch.equal(val, out[0][1]), env
 
 
 @pytest.mark.parametrize("nb,N", [(97, 3001), (700, 50_001), (4096, 3000), (4096, 200_000), (1000, 40_000)])
