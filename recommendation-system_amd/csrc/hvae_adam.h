@@ -179,7 +179,8 @@ static inline RowMap row_map(int64_t H) {
 
 // float4 column i of a row: replay steps (from, to] with g = 0 (constants from the step table,
 // loaded kTabAhead at a time), then, if `step`, one more step with constants kx and gradient gx. Split into load /
-// math / store so that the row loops below can keep U row groups' loads in flight together.
+// math / store so that a caller can load a row's first column together with its stamp (k_adam_lazy), keep two
+// entries' loads in flight (hvae_mlp.hip) or store p alone (k_adam_catchup_csr).
 struct ColState {
   float4 p, m, v;
 };
@@ -230,17 +231,6 @@ __device__ __forceinline__ void col_math_lazy(const AdamArgs& a, const float2* _
     adam_elem(pp.z, mm.z, vv.z, gx.z, kx);
     adam_elem(pp.w, mm.w, vv.w, gx.w, kx);
   }
-}
-__device__ __forceinline__ void col_math(const AdamArgs& a, const float2* __restrict__ tab, ColState& cs, int from,
-                                         int to, bool step, const AdamK& kx, float4 gx) {
-  col_math_lazy(a, tab, cs, from, from, to, step, kx, gx);
-}
-__device__ __forceinline__ void col_update(const AdamArgs& a, const float2* __restrict__ tab, float* __restrict__ p,
-                                           float* __restrict__ m, float* __restrict__ v, int64_t i, int from, int to,
-                                           bool step, const AdamK& kx, float4 gx) {
-  ColState c = col_load(p, m, v, i);
-  col_math(a, tab, c, from, to, step, kx, gx);
-  col_store(p, m, v, i, c);
 }
 
 static inline AdamArgs to_args(const hvae_adam* c) {

@@ -61,9 +61,10 @@ constexpr int kTicketPool = 1 << 16, kTicketSlice = 256;
 constexpr int kRowSqParts = HVAE_ROWSQ_PARTS;  // fp64 partial sums of squares per W1 gradient row (hvae_rowgrad.rowsq)
 unsigned* ticket_slice();  // nullptr (error set) on failure
 
-// A/B knobs (HVAE_DEC_*, HVAE_TOPK_*, HVAE_TK_*, HVAE_GEMM_* in the environment) are read only by variant builds
-// compiled with -DHVAE_AB=1 (scripts/build_ab.sh -> build_var/libhvae_ab.so); the product library ignores the
-// environment and always runs its defaults.
+// A/B knobs (HVAE_DEC_*, HVAE_TOPK_*, HVAE_TK_*, HVAE_GEMM_*, HVAE_MLP_*, HVAE_RG_SORTED in the environment) are read
+// only by variant builds compiled with -DHVAE_AB=1 (make lib-ab -> build_var/libhvae_ab.so); the product library
+// ignores the environment and always runs its defaults. HVAE_AB is always defined: guard with #if HVAE_AB, never
+// #ifdef.
 #ifndef HVAE_AB
 #define HVAE_AB 0
 #endif

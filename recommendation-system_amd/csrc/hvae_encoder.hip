@@ -1039,8 +1039,7 @@ extern "C" int hvae_w1_rowgrad_apply(const float* da, int64_t H, const hvae_rowg
                "hvae_w1_rowgrad_apply: part scratch too small for H");
   hipStream_t st = as_stream(stream);
   ProbeScope probe("rowgrad_apply", st);
-  double* rowsq = rg->rowsq;
-  if (const char* e = ab_getenv("HVAE_ROWSQ")) if (std::atoi(e) == 0) rowsq = nullptr;  // A/B: the clip reads rows
+  double* rowsq = rg->rowsq;  // NULL: the clip reads the rows
   if (rg->cap <= kPlanSmallCap) {
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(rg->cap, 4), 1024));
     HVAE_NV_DISPATCH(H, (k_rg_apply_seg<NV><<<grid, 256, 0, st>>>(rg->n_unique, rg->seg_off, rg->contrib_row,

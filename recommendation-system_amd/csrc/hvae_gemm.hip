@@ -1314,7 +1314,7 @@ extern "C" int hvae_gemm_f32(int trans_a, int trans_b, int64_t M, int64_t N, int
   (pl.bm == 64 ? (k_gemm_fast<TA_, TB_, 64, 64><<<grid, 256, 0, st>>>(g))       \
                : (k_gemm_fast<TA_, TB_, 32, 32><<<grid, 256, 0, st>>>(g)))
     if (trans_a) HVAE_FAST_CALL(true, false);
-#ifdef HVAE_AB
+#if HVAE_AB
     else if (trans_b) HVAE_FAST_CALL(false, true);
     else HVAE_FAST_CALL(false, false);
 #endif

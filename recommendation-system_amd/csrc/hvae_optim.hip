@@ -189,31 +189,13 @@ __global__ void __launch_bounds__(256) k_adam_flat(AdamArgs a, float* __restrict
 }
 
 constexpr int kCatchupBlocks = 1024;  // k_adam_catchup_csr: blocks to aim for over a small batch
-// Row groups (rows x float4 columns) per barrier in the row kernels. Four groups' loads in flight per barrier
-// (HVAE_ADAM_UNROLL=4, A/B build) ran slower than one everywhere -- Syn-10M 11.55-11.62 vs 11.52 ms per step,
-// Syn-1M 1.208 vs 1.194, All_Beauty 0.143 vs 0.134 (adam_rows 20 vs 13 us; profiles/r04_adam_unroll_ab.jsonl):
-// the unrolled kernels hold 164 VGPRs (3 waves per SIMD) and a quarter of the blocks.
-constexpr int kAdamUnroll = 1;
-// A/B (HVAE_AB builds): HVAE_ADAM_UNROLL=4 keeps four row groups in flight, HVAE_CATCHUP_PONLY=0 stores m, v in
-// the CSR catch-up too
-static int adam_unroll() {
-  const char* e = ab_getenv("HVAE_ADAM_UNROLL");
-  return e && std::atoi(e) == 4 ? 4 : kAdamUnroll;
-}
-static int catchup_p_only() {
-  const char* e = ab_getenv("HVAE_CATCHUP_PONLY");
-  return e && std::atoi(e) == 0 ? 0 : 1;
-}
-#ifdef HVAE_AB
-#define HVAE_ADAM_U_CALL(U_, CALL) \
-  do { if ((U_) == 4) { constexpr int U = 4; CALL; } else { constexpr int U = kAdamUnroll; CALL; } } while (0)
-#else
-#define HVAE_ADAM_U_CALL(U_, CALL) do { constexpr int U = kAdamUnroll; CALL; } while (0)
-#endif
+
+// The row kernels below take one row group (rm.rpb rows x float4 columns) per barrier. Four groups' loads in flight
+// per barrier ran slower everywhere (profiles/r04_adam_unroll_ab.jsonl): 164 VGPRs, three waves per
+// SIMD and a quarter of the blocks.
 
 // Bring rows up to the completed step count *step: the batch's rows (item_of /
 // n_unique) or, with item_of == NULL, all N rows.
-template <int U>
 __global__ void __launch_bounds__(256) k_adam_catchup(AdamArgs a, const float2* __restrict__ tab, float* p, float* m,
                                                       float* v, int32_t* __restrict__ last_step,
                                                       const int32_t* __restrict__ item_of,
@@ -224,36 +206,20 @@ __global__ void __launch_bounds__(256) k_adam_catchup(AdamArgs a, const float2* 
   const int64_t H4 = H / 4;
   const int rr = threadIdx.x / rm.h4s, c0 = threadIdx.x % rm.h4s;
   const AdamK none{};
-  const int64_t span = (int64_t)rm.rpb * U;
-  for (int64_t g0 = (int64_t)blockIdx.x * span; g0 < nrows; g0 += (int64_t)gridDim.x * span) {
-    int64_t j[U];
-    int from[U], pst[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t r = g0 + (int64_t)u * rm.rpb + rr;
-      const bool act = rr < rm.rpb && r < nrows;
-      j[u] = act ? (item_of ? (int64_t)item_of[r] : r) : 0;
-      const int32_t ls = act ? last_step[j[u]] : to;
-      from[u] = ls_mv(ls);
-      pst[u] = ls_p(ls);
-    }
-    for (int64_t c = c0; c < H4; c += rm.h4s) {
-      ColState cs[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (from[u] < to) cs[u] = col_load(p, m, v, j[u] * H4 + c);
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (from[u] < to)
-          col_math_lazy(a, tab, cs[u], from[u], pst[u], to, false, none, make_float4(0.f, 0.f, 0.f, 0.f));
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (from[u] < to) col_store(p, m, v, j[u] * H4 + c, cs[u]);
-    }
+  for (int64_t g0 = (int64_t)blockIdx.x * rm.rpb; g0 < nrows; g0 += (int64_t)gridDim.x * rm.rpb) {
+    const int64_t r = g0 + rr;
+    const bool act = rr < rm.rpb && r < nrows;
+    const int64_t j = act ? (item_of ? (int64_t)item_of[r] : r) : 0;
+    const int32_t ls = act ? last_step[j] : to;
+    const int from = ls_mv(ls), pst = ls_p(ls);
+    if (from < to)
+      for (int64_t c = c0; c < H4; c += rm.h4s) {
+        ColState cs = col_load(p, m, v, j * H4 + c);
+        col_math_lazy(a, tab, cs, from, pst, to, false, none, make_float4(0.f, 0.f, 0.f, 0.f));
+        col_store(p, m, v, j * H4 + c, cs);
+      }
     __syncthreads();
-#pragma unroll
-    for (int u = 0; u < U; ++u)
-      if (c0 == 0 && from[u] < to) last_step[j[u]] = to;
+    if (c0 == 0 && from < to) last_step[j] = to;
   }
 }
 
@@ -268,14 +234,16 @@ __global__ void __launch_bounds__(256) k_adam_catchup(AdamArgs a, const float2* 
 // With a deferred step recorded (hdr != NULL, ABI 5), a listed row that carries it (last_step bit 30) is claimed
 // like any other and takes that step here -- its missed steps replayed, then step hdr->t with its gradient row
 // times hdr->coef, k_adam_lazy's float operations -- and stores p, m and v (the caller passes to == hdr->t).
-template <int U>
 __global__ void __launch_bounds__(256) k_adam_catchup_csr(AdamArgs a, const float2* __restrict__ tab, float* p,
                                                           float* m, float* v, int32_t* __restrict__ last_step,
-                                                          hvae_csr_batch x, int64_t H, int S, int p_only_arg,
+                                                          hvae_csr_batch x, int64_t H, int S,
                                                           const int32_t* __restrict__ pend_slot,
                                                           const PendHdr* __restrict__ hdr) {
   __shared__ int s_j[256], s_from[256], s_pst[256], s_slot[256];
   __shared__ int s_n;
+  // The work loop keeps the load / math / store phases of the unroll experiment at one column per thread: written
+  // as one scalar sequence per column it compiles to 92-94 VGPRs against 79 (five waves per SIMD against six).
+  constexpr int U = 1;
   const int to = (int)load_step(a.step_dev);
   const int64_t H4 = H / 4;
   const AdamK none{};
@@ -286,7 +254,7 @@ __global__ void __launch_bounds__(256) k_adam_catchup_csr(AdamArgs a, const floa
   const float pcoef = pend_on ? hdr->coef : 1.f;
   const AdamK kp = pend_on ? adam_consts_tab(a, tab[to]) : none;
   // p alone moves ahead unless weight decay couples m, v to p, or m, v are too far behind to say so in the stamp
-  const bool p_only_ok = a.wd == 0.0 && p_only_arg;
+  const bool p_only_ok = a.wd == 0.0;
   const int sl = (int)(blockIdx.x % (unsigned)S);
   for (int64_t b = blockIdx.x / S; b < x.nb; b += gridDim.x / S) {
     const int64_t r = batch_row(x.rows, x.rows_offset, b);
@@ -380,7 +348,6 @@ static int lazy_sweep_period(int64_t N) {
   if (HVAE_LAZY_SWEEP > 0) return HVAE_LAZY_SWEEP;
   return N >= kLazySweepLargeN ? 32 : 8;
 }
-template <int U>
 __global__ void __launch_bounds__(256) k_adam_lazy(AdamArgs a, float2* __restrict__ tab, float* __restrict__ p,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    int32_t* __restrict__ last_step, const float* __restrict__ rows,
@@ -401,7 +368,6 @@ __global__ void __launch_bounds__(256) k_adam_lazy(AdamArgs a, float2* __restric
   const int nu = *n_unique;
   const int64_t H4 = H / 4;
   const int rr = threadIdx.x / rm.h4s, cc = threadIdx.x % rm.h4s;
-  const int64_t span = (int64_t)rm.rpb * U;
   if (hdr != nullptr && (int)blockIdx.x < nb_rows) {
     // deferred (hvae_adam_lazy_defer): the gradient rows are recorded as pending, nothing moves; the next
     // catch-up or k_adam_pending applies step t to each of them
@@ -415,102 +381,64 @@ __global__ void __launch_bounds__(256) k_adam_lazy(AdamArgs a, float2* __restric
       last_step[j] = last_step[j] | kPendBit;
     }
   } else if ((int)blockIdx.x < nb_rows) {
-    for (int64_t g0 = (int64_t)blockIdx.x * span; g0 < nu; g0 += (int64_t)nb_rows * span) {
-      int64_t sidx[U], j[U];
-      int from[U], pst[U];
-      bool act[U];
+    for (int64_t g0 = (int64_t)blockIdx.x * rm.rpb; g0 < nu; g0 += (int64_t)nb_rows * rm.rpb) {
+      const int64_t s = g0 + rr;
+      const bool act = rr < rm.rpb && s < nu;
+      const int64_t j = act ? (int64_t)item_of[s] : 0;
       // the row's stamp, its first column's (p, m, v) and gradient are loaded together (one round trip after
       // item_of instead of two)
-      ColState cs0[U];
-      float4 gv0[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        sidx[u] = g0 + (int64_t)u * rm.rpb + rr;
-        act[u] = rr < rm.rpb && sidx[u] < nu;
-        j[u] = act[u] ? (int64_t)item_of[sidx[u]] : 0;
-        const int32_t ls = act[u] ? last_step[j[u]] : t;
-        if (act[u] && cc < H4) {
-          cs0[u] = col_load(p, m, v, j[u] * H4 + cc);
-          gv0[u] = *reinterpret_cast<const float4*>(rows + sidx[u] * H + 4 * cc);
+      const int32_t ls = act ? last_step[j] : t;
+      ColState cs;
+      float4 g;
+      if (act) {
+        cs = col_load(p, m, v, j * H4 + cc);
+        g = *reinterpret_cast<const float4*>(rows + s * H + 4 * cc);
+      }
+      const int from = ls_mv(ls), pst = ls_p(ls);
+      if (act)
+        for (int64_t c = cc; c < H4; c += rm.h4s) {
+          if (c != cc) {
+            cs = col_load(p, m, v, j * H4 + c);
+            g = *reinterpret_cast<const float4*>(rows + s * H + 4 * c);
+          }
+          g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
+          col_math_lazy(a, tab, cs, from, pst, t - 1, true, k, g);
+          col_store(p, m, v, j * H4 + c, cs);
         }
-        from[u] = ls_mv(ls);
-        pst[u] = ls_p(ls);
-      }
-      for (int64_t c = cc; c < H4; c += rm.h4s) {
-        ColState cs[U];
-        float4 gv[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (act[u]) {
-            if (c == cc) {
-              cs[u] = cs0[u];
-              gv[u] = gv0[u];
-            } else {
-              cs[u] = col_load(p, m, v, j[u] * H4 + c);
-              gv[u] = *reinterpret_cast<const float4*>(rows + sidx[u] * H + 4 * c);
-            }
-          }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (act[u]) {
-            float4 g = gv[u];
-            g.x *= coef; g.y *= coef; g.z *= coef; g.w *= coef;
-            col_math_lazy(a, tab, cs[u], from[u], pst[u], t - 1, true, k, g);
-          }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (act[u]) col_store(p, m, v, j[u] * H4 + c, cs[u]);
-      }
       __syncthreads();
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (act[u] && cc == 0) last_step[j[u]] = t;
+      if (act && cc == 0) last_step[j] = t;
     }
   } else if ((int)blockIdx.x < nb_rows + nb_sweep) {
     const int64_t chunk = (N + period - 1) / period;
     const int64_t r0 = (int64_t)((t - 1) % period) * chunk, r1 = min(N, r0 + chunk);
-    for (int64_t g0 = r0 + (int64_t)(blockIdx.x - nb_rows) * span; g0 < r1; g0 += (int64_t)nb_sweep * span) {
-      int64_t j[U];
-      int from[U], pst[U];
-      bool act[U];
+    for (int64_t g0 = r0 + (int64_t)(blockIdx.x - nb_rows) * rm.rpb; g0 < r1; g0 += (int64_t)nb_sweep * rm.rpb) {
+      const int64_t j = g0 + rr;
+      bool act = rr < rm.rpb && j < r1;
+      int from = t, pst = t;
       // the row's slot, stamp and first column's (p, m, v) are loaded together, before it is known whether the row
       // is this group's (no gradient) and stale: the speculative loads of the skipped rows cost bytes, not a round
       // trip
-      ColState cs0[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        j[u] = g0 + (int64_t)u * rm.rpb + rr;
-        act[u] = rr < rm.rpb && j[u] < r1;
-        from[u] = pst[u] = t;
-        if (act[u]) {
-          const int sl = slot_of[j[u]];
-          const int32_t ls = last_step[j[u]];
-          if (cc < H4) cs0[u] = col_load(p, m, v, j[u] * H4 + cc);
-          if (sl >= 0 && sl < nu && item_of[sl] == (int32_t)j[u]) {
-            act[u] = false;  // has a gradient: first group's row
-          } else {
-            from[u] = ls_mv(ls);
-            pst[u] = ls_p(ls);
-          }
+      ColState cs;
+      if (act) {
+        const int sl = slot_of[j];
+        const int32_t ls = last_step[j];
+        cs = col_load(p, m, v, j * H4 + cc);
+        if (sl >= 0 && sl < nu && item_of[sl] == (int32_t)j) {
+          act = false;  // has a gradient: first group's row
+        } else {
+          from = ls_mv(ls);
+          pst = ls_p(ls);
         }
-        act[u] = act[u] && from[u] < t;
       }
-      for (int64_t c = cc; c < H4; c += rm.h4s) {
-        ColState cs[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (act[u]) cs[u] = c == cc ? cs0[u] : col_load(p, m, v, j[u] * H4 + c);
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (act[u]) col_math_lazy(a, tab, cs[u], from[u], pst[u], t - 1, true, k, make_float4(0.f, 0.f, 0.f, 0.f));
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-          if (act[u]) col_store(p, m, v, j[u] * H4 + c, cs[u]);
-      }
+      act = act && from < t;
+      if (act)
+        for (int64_t c = cc; c < H4; c += rm.h4s) {
+          if (c != cc) cs = col_load(p, m, v, j * H4 + c);
+          col_math_lazy(a, tab, cs, from, pst, t - 1, true, k, make_float4(0.f, 0.f, 0.f, 0.f));
+          col_store(p, m, v, j * H4 + c, cs);
+        }
       __syncthreads();
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (act[u] && cc == 0) last_step[j[u]] = t;
+      if (act && cc == 0) last_step[j] = t;
     }
   } else {
     // the small dense parameters: float4 where the segment is 16-B aligned, scalar tail
@@ -630,9 +558,10 @@ static unsigned clip_blocks(const ClipArgs& a, const hvae_rowgrad* rg) {
   return (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(units, 256 * 4), kNormBlocks));
 }
 
+// cfg and tab (both or neither): record the coming Adam step's scalars in tab[step + 1]
 static int clip_launch(const float* g_dense, int64_t n_dense, const hvae_rowgrad* rg, int64_t H, float max_norm,
                        float* norm_out, float* coef_out, int64_t* step, int64_t* step_snap, int64_t* boff,
-                       int64_t advance, void* ws, size_t ws_bytes, void* stream) {
+                       int64_t advance, const hvae_adam* cfg, float* tab, void* ws, size_t ws_bytes, void* stream) {
   HVAE_REQUIRE(coef_out && n_dense >= 0 && (n_dense == 0 || g_dense), "hvae_clip_grad_norm: bad args");
   HVAE_REQUIRE(!rg || (rg->rows && rg->n_unique && H > 0), "hvae_clip_grad_norm: bad rowgrad");
   if (!ws || ws_bytes < kNormBlocks * sizeof(double))
@@ -641,11 +570,13 @@ static int clip_launch(const float* g_dense, int64_t n_dense, const hvae_rowgrad
   a.g = g_dense; a.n = n_dense;
   a.rows = rg ? rg->rows : nullptr; a.n_unique = rg ? rg->n_unique : nullptr; a.H = H;
   a.rowsq = rg ? rg->rowsq : nullptr;
-  if (const char* e = ab_getenv("HVAE_ROWSQ")) if (std::atoi(e) == 0) a.rowsq = nullptr;
   a.part = (double*)ws;
   if (!(a.ticket = ticket_slice())) return HVAE_ERR_HIP;
   a.max_norm = max_norm; a.norm_out = norm_out; a.coef_out = coef_out;
   a.step = step; a.step_snap = step_snap; a.boff = boff; a.advance = advance;
+  if (cfg) {
+    a.tab = (float2*)tab; a.lr = cfg->lr; a.b1 = cfg->beta1; a.b2 = cfg->beta2;
+  }
   ProbeScope probe("clip", as_stream(stream));
   k_clip_norm<<<clip_blocks(a, rg), 256, 0, as_stream(stream)>>>(a);
   HVAE_LAUNCH_CHECK("k_clip_norm");
@@ -655,8 +586,8 @@ static int clip_launch(const float* g_dense, int64_t n_dense, const hvae_rowgrad
 extern "C" int hvae_clip_grad_norm(const float* g_dense, int64_t n_dense, const hvae_rowgrad* rg,
                                    int64_t H, float max_norm, float* norm_out, float* coef_out,
                                    void* ws, size_t ws_bytes, void* stream) {
-  return clip_launch(g_dense, n_dense, rg, H, max_norm, norm_out, coef_out, nullptr, nullptr, nullptr, 0, ws,
-                     ws_bytes, stream);
+  return clip_launch(g_dense, n_dense, rg, H, max_norm, norm_out, coef_out, nullptr, nullptr, nullptr, 0, nullptr,
+                     nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int hvae_clip_grad_norm_step(const float* g_dense, int64_t n_dense, const hvae_rowgrad* rg,
@@ -666,7 +597,7 @@ extern "C" int hvae_clip_grad_norm_step(const float* g_dense, int64_t n_dense, c
   HVAE_REQUIRE(step_dev && step_snap, "hvae_clip_grad_norm_step: null step counters");
   HVAE_REQUIRE(advance == 0 || boff, "hvae_clip_grad_norm_step: advance without boff");
   return clip_launch(g_dense, n_dense, rg, H, max_norm, norm_out, coef_out, step_dev, step_snap, boff, advance,
-                     ws, ws_bytes, stream);
+                     nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int hvae_clip_grad_norm_step_adam(const float* g_dense, int64_t n_dense, const hvae_rowgrad* rg,
@@ -676,24 +607,8 @@ extern "C" int hvae_clip_grad_norm_step_adam(const float* g_dense, int64_t n_den
                                              void* stream) {
   HVAE_REQUIRE(step_dev && step_snap && cfg && tab, "hvae_clip_grad_norm_step_adam: null step counters / cfg / tab");
   HVAE_REQUIRE(advance == 0 || boff, "hvae_clip_grad_norm_step_adam: advance without boff");
-  HVAE_REQUIRE(coef_out && n_dense >= 0 && (n_dense == 0 || g_dense), "hvae_clip_grad_norm: bad args");
-  HVAE_REQUIRE(!rg || (rg->rows && rg->n_unique && H > 0), "hvae_clip_grad_norm: bad rowgrad");
-  if (!ws || ws_bytes < kNormBlocks * sizeof(double))
-    HVAE_FAIL(HVAE_ERR_WORKSPACE, "hvae_clip_grad_norm: workspace too small");
-  ClipArgs a{};
-  a.g = g_dense; a.n = n_dense;
-  a.rows = rg ? rg->rows : nullptr; a.n_unique = rg ? rg->n_unique : nullptr; a.H = H;
-  a.rowsq = rg ? rg->rowsq : nullptr;
-  if (const char* e = ab_getenv("HVAE_ROWSQ")) if (std::atoi(e) == 0) a.rowsq = nullptr;
-  a.part = (double*)ws;
-  if (!(a.ticket = ticket_slice())) return HVAE_ERR_HIP;
-  a.max_norm = max_norm; a.norm_out = norm_out; a.coef_out = coef_out;
-  a.step = step_dev; a.step_snap = step_snap; a.boff = boff; a.advance = advance;
-  a.tab = (float2*)tab; a.lr = cfg->lr; a.b1 = cfg->beta1; a.b2 = cfg->beta2;
-  ProbeScope probe("clip", as_stream(stream));
-  k_clip_norm<<<clip_blocks(a, rg), 256, 0, as_stream(stream)>>>(a);
-  HVAE_LAUNCH_CHECK("k_clip_norm");
-  return HVAE_OK;
+  return clip_launch(g_dense, n_dense, rg, H, max_norm, norm_out, coef_out, step_dev, step_snap, boff, advance, cfg,
+                     tab, ws, ws_bytes, stream);
 }
 
 extern "C" int hvae_adam_dense(const hvae_adam* cfg, float* p, float* m, float* v, const float* g,
@@ -750,18 +665,19 @@ extern "C" int hvae_adam_lazy_catchup(const hvae_adam* cfg, const float* tab, fl
   if (N == 0) return HVAE_OK;
   const int64_t nrows = rows ? rows->cap : N;
   const RowMap rm = row_map(H);
-  const int uu = adam_unroll();
-  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nrows, (int64_t)rm.rpb * uu), 16384));
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(cdiv(nrows, (int64_t)rm.rpb), 16384));
   ProbeScope probe("adam_catchup", as_stream(stream));
-  HVAE_ADAM_U_CALL(uu, (k_adam_catchup<U><<<grid, 256, 0, as_stream(stream)>>>(to_args(cfg), (const float2*)tab, p, m, v,
-                                                      last_step, rows ? rows->item_of : nullptr,
-                                                      rows ? rows->n_unique : nullptr, N, H, rm)));
+  k_adam_catchup<<<grid, 256, 0, as_stream(stream)>>>(to_args(cfg), (const float2*)tab, p, m, v, last_step,
+                                                      rows ? rows->item_of : nullptr,
+                                                      rows ? rows->n_unique : nullptr, N, H, rm);
   HVAE_LAUNCH_CHECK("k_adam_catchup");
   return HVAE_OK;
 }
 
-extern "C" int hvae_adam_lazy_catchup_csr(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v,
-                                          int32_t* last_step, const hvae_csr_batch* x, int64_t H, void* stream) {
+// pend != NULL: listed rows that carry the recorded step take it here (k_adam_catchup_csr)
+static int catchup_csr_launch(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v,
+                              int32_t* last_step, const hvae_csr_batch* x, int64_t H, const hvae_adam_pend* pend,
+                              void* stream) {
   HVAE_REQUIRE(cfg && cfg->step_dev && tab && p && m && v && last_step && H % 4 == 0 && x && x->row_ptr &&
                    x->col_idx,
                "hvae_adam_lazy_catchup_csr: bad args");
@@ -770,30 +686,23 @@ extern "C" int hvae_adam_lazy_catchup_csr(const hvae_adam* cfg, const float* tab
   const int S = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(kCatchupBlocks, x->nb), 64));
   const unsigned grid = (unsigned)(std::min<int64_t>(x->nb, 16384) * S);
   ProbeScope probe("adam_catchup", as_stream(stream));
-  const int pon = catchup_p_only();
-  HVAE_ADAM_U_CALL(adam_unroll(), (k_adam_catchup_csr<U><<<grid, 256, 0, as_stream(stream)>>>(
-                                      to_args(cfg), (const float2*)tab, p, m, v, last_step, *x, H, S, pon, nullptr,
-                                      nullptr)));
+  k_adam_catchup_csr<<<grid, 256, 0, as_stream(stream)>>>(to_args(cfg), (const float2*)tab, p, m, v, last_step, *x, H,
+                                                          S, pend ? pend->slot_of : nullptr,
+                                                          pend ? (const PendHdr*)pend->hdr : nullptr);
   HVAE_LAUNCH_CHECK("k_adam_catchup_csr");
   return HVAE_OK;
+}
+
+extern "C" int hvae_adam_lazy_catchup_csr(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v,
+                                          int32_t* last_step, const hvae_csr_batch* x, int64_t H, void* stream) {
+  return catchup_csr_launch(cfg, tab, p, m, v, last_step, x, H, nullptr, stream);
 }
 
 extern "C" int hvae_adam_lazy_catchup_csr_pending(const hvae_adam* cfg, const float* tab, float* p, float* m,
                                                   float* v, int32_t* last_step, const hvae_csr_batch* x, int64_t H,
                                                   const hvae_adam_pend* pend, void* stream) {
-  HVAE_REQUIRE(cfg && cfg->step_dev && tab && p && m && v && last_step && H % 4 == 0 && x && x->row_ptr &&
-                   x->col_idx && pend && pend->slot_of && pend->hdr,
-               "hvae_adam_lazy_catchup_csr_pending: bad args");
-  if (x->nb == 0) return HVAE_OK;
-  const int S = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv(kCatchupBlocks, x->nb), 64));
-  const unsigned grid = (unsigned)(std::min<int64_t>(x->nb, 16384) * S);
-  ProbeScope probe("adam_catchup", as_stream(stream));
-  const int pon = catchup_p_only();
-  k_adam_catchup_csr<kAdamUnroll><<<grid, 256, 0, as_stream(stream)>>>(
-      to_args(cfg), (const float2*)tab, p, m, v, last_step, *x, H, S, pon, pend->slot_of,
-      (const PendHdr*)pend->hdr);
-  HVAE_LAUNCH_CHECK("k_adam_catchup_csr");
-  return HVAE_OK;
+  HVAE_REQUIRE(pend && pend->slot_of && pend->hdr, "hvae_adam_lazy_catchup_csr_pending: bad pend");
+  return catchup_csr_launch(cfg, tab, p, m, v, last_step, x, H, pend, stream);
 }
 
 extern "C" int hvae_adam_lazy_pending(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v,
@@ -819,7 +728,33 @@ extern "C" int hvae_adam_lazy_pending(const hvae_adam* cfg, const float* tab, fl
 
 static int adam_lazy_launch(const hvae_adam* cfg, float* tab, int64_t tab_len, float* p, float* m, float* v,
                             int32_t* last_step, const hvae_rowgrad* rg, int64_t H, const float* g_dense,
-                            int64_t dense_off, int64_t n_dense, const hvae_adam_pend* pend, void* stream);
+                            int64_t dense_off, int64_t n_dense, const hvae_adam_pend* pend, void* stream) {
+  HVAE_REQUIRE(cfg && cfg->step_dev && tab && p && m && v && last_step && rg && rg->rows && rg->item_of &&
+                   rg->n_unique,
+               "hvae_adam_lazy: bad args");
+  HVAE_REQUIRE(H % 4 == 0 && ((uintptr_t)p % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
+               "hvae_adam_lazy: H %% 4 and 16-B alignment required");
+  HVAE_REQUIRE(n_dense == 0 || (g_dense && dense_off >= rg->n_items * H), "hvae_adam_lazy: dense overlaps W1t");
+  HVAE_REQUIRE(tab_len >= 2, "hvae_adam_lazy: step table too short");
+  HVAE_REQUIRE(tab_len <= ((int64_t)1 << kStepBits), "hvae_adam_lazy: step table longer than last_step's 2^24 steps");
+  const int64_t N = rg->n_items;
+  HVAE_REQUIRE(rg->slot_of, "hvae_adam_lazy: rowgrad without slot_of");
+  const RowMap rm = row_map(H);
+  // deferred: the row blocks only record the rows (one thread a row) and the sweep waits for k_adam_pending
+  const int64_t b_rows = pend ? std::max<int64_t>(1, std::min<int64_t>(cdiv(rg->cap, 256), 1024))
+                              : std::max<int64_t>(1, std::min<int64_t>(cdiv(rg->cap, (int64_t)rm.rpb), 4096));
+  const int period = lazy_sweep_period(N);
+  const int64_t b_sweep =
+      pend ? 0 : std::max<int64_t>(1, std::min<int64_t>(cdiv(cdiv(N, period), (int64_t)rm.rpb), 4096));
+  const int64_t b_dense = std::min<int64_t>(cdiv(cdiv(n_dense, 4), 256), 512);
+  ProbeScope probe("adam_rows", as_stream(stream));
+  k_adam_lazy<<<(unsigned)(b_rows + b_sweep + b_dense), 256, 0, as_stream(stream)>>>(
+      to_args(cfg), (float2*)tab, p, m, v, last_step, rg->rows, rg->slot_of, rg->item_of, rg->n_unique, N, H,
+      g_dense, dense_off, n_dense, (int)b_rows, (int)b_sweep, period, rm, pend ? pend->slot_of : nullptr,
+      pend ? pend->item_of : nullptr, pend ? (PendHdr*)pend->hdr : nullptr);
+  HVAE_LAUNCH_CHECK("k_adam_lazy");
+  return HVAE_OK;
+}
 
 extern "C" int hvae_adam_lazy(const hvae_adam* cfg, float* tab, int64_t tab_len, float* p, float* m, float* v,
                               int32_t* last_step, const hvae_rowgrad* rg, int64_t H, const float* g_dense,
@@ -833,37 +768,6 @@ extern "C" int hvae_adam_lazy_defer(const hvae_adam* cfg, float* tab, int64_t ta
                                     int64_t dense_off, int64_t n_dense, const hvae_adam_pend* pend, void* stream) {
   HVAE_REQUIRE(pend && pend->slot_of && pend->item_of && pend->hdr, "hvae_adam_lazy_defer: bad pend");
   return adam_lazy_launch(cfg, tab, tab_len, p, m, v, last_step, rg, H, g_dense, dense_off, n_dense, pend, stream);
-}
-
-static int adam_lazy_launch(const hvae_adam* cfg, float* tab, int64_t tab_len, float* p, float* m, float* v,
-                            int32_t* last_step, const hvae_rowgrad* rg, int64_t H, const float* g_dense,
-                            int64_t dense_off, int64_t n_dense, const hvae_adam_pend* pend, void* stream) {
-  HVAE_REQUIRE(cfg && cfg->step_dev && tab && p && m && v && last_step && rg && rg->rows && rg->item_of &&
-                   rg->n_unique,
-               "hvae_adam_lazy: bad args");
-  HVAE_REQUIRE(H % 4 == 0 && ((uintptr_t)p % 16) == 0 && ((uintptr_t)m % 16) == 0 && ((uintptr_t)v % 16) == 0,
-               "hvae_adam_lazy: H %% 4 and 16-B alignment required");
-  HVAE_REQUIRE(n_dense == 0 || (g_dense && dense_off >= rg->n_items * H), "hvae_adam_lazy: dense overlaps W1t");
-  HVAE_REQUIRE(tab_len >= 2, "hvae_adam_lazy: step table too short");
-  HVAE_REQUIRE(tab_len <= ((int64_t)1 << kStepBits), "hvae_adam_lazy: step table longer than last_step's 2^24 steps");
-  const int64_t N = rg->n_items;
-  HVAE_REQUIRE(rg->slot_of, "hvae_adam_lazy: rowgrad without slot_of");
-  const RowMap rm = row_map(H);
-  const int uu = adam_unroll();
-  // deferred: the row blocks only record the rows (one thread a row) and the sweep waits for k_adam_pending
-  const int64_t b_rows = pend ? std::max<int64_t>(1, std::min<int64_t>(cdiv(rg->cap, 256), 1024))
-                              : std::max<int64_t>(1, std::min<int64_t>(cdiv(rg->cap, (int64_t)rm.rpb * uu), 4096));
-  const int period = lazy_sweep_period(N);
-  const int64_t b_sweep =
-      pend ? 0 : std::max<int64_t>(1, std::min<int64_t>(cdiv(cdiv(N, period), (int64_t)rm.rpb * uu), 4096));
-  const int64_t b_dense = std::min<int64_t>(cdiv(cdiv(n_dense, 4), 256), 512);
-  ProbeScope probe("adam_rows", as_stream(stream));
-  HVAE_ADAM_U_CALL(uu, (k_adam_lazy<U><<<(unsigned)(b_rows + b_sweep + b_dense), 256, 0, as_stream(stream)>>>(
-      to_args(cfg), (float2*)tab, p, m, v, last_step, rg->rows, rg->slot_of, rg->item_of, rg->n_unique, N, H,
-      g_dense, dense_off, n_dense, (int)b_rows, (int)b_sweep, period, rm, pend ? pend->slot_of : nullptr,
-      pend ? pend->item_of : nullptr, pend ? (PendHdr*)pend->hdr : nullptr)));
-  HVAE_LAUNCH_CHECK("k_adam_lazy");
-  return HVAE_OK;
 }
 
 extern "C" int hvae_adam_lazy_sweep_period(int64_t N) { return hvae::lazy_sweep_period(N); }
