@@ -61,8 +61,8 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 #define DEC5_G1PRIO 0  // A/B: s_setprio 1 over the P32 producer's GEMM1 MFMAs only, 0 again before its softmax tail
 #endif
 #ifndef DEC5_DMA_B
-#define DEC5_DMA_B 4  // of each (ug, dh)'s 12 LDS-DMA pieces per tile, how many the consumer wave issues (the producer's
-                      // trimmed loop takes 8: DESIGN.md 4.1a, round 7)
+#define DEC5_DMA_B 4  // of a D quarter's 12 LDS-DMA pieces per tile, how many its consumer wave issues: at most the 6
+                      // of item half 0, which it refills early (k_dec5_bf16's header); producer q takes the others
 #endif
 // Timing-ablation builds only (scripts/build_variant5.sh; outputs invalid by construction), a bit mask:
 // 1 no LDS-DMA pieces in the loop (and no vmcnt waits), 2 no per-tile barrier, 4 no exponentials / P out,
@@ -71,8 +71,9 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 #ifndef DEC5_ABL
 #define DEC5_ABL 0
 #endif
-// Placement of the LDS-DMA pieces: producer piece i at GEMM1 k-step DEC5_PDMA_AT + DEC5_DMA_STRIDE i, consumer piece
-// i at GEMM2 MFMA DEC5_CDMA_AT + DEC5_DMA_STRIDE i (as early as possible: the fill latency is the sweep's limit)
+// Placement of the LDS-DMA pieces: producer piece i at GEMM1 k-step DEC5_PDMA_AT + DEC5_DMA_STRIDE i; consumer piece
+// i in the gap after GEMM2 MFMA 11 + DEC5_CDMA_AT + DEC5_DMA_STRIDE i of the tile's 24 (MFMA 11 is the last to take
+// item half 0, whose bytes the piece overwrites; as early as possible: the fill latency is the sweep's limit)
 #ifndef DEC5_PDMA_AT
 #define DEC5_PDMA_AT 0
 #endif
@@ -82,7 +83,7 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
 #ifndef DEC5_CDMA_AT
 #define DEC5_CDMA_AT 0
 #endif
-// DEC5_RSTAGE=1 (A/B): the producer stages its 12 - DEC5_DMA_B pieces of its (ug, dh) through registers (buffer_load_dwordx4
+// DEC5_RSTAGE=1 (A/B): the producer stages its 12 - DEC5_DMA_B pieces of its D quarter through registers (buffer_load_dwordx4
 // to VGPRs one tile ahead, ds_write_b128 into the image after the barrier that frees the slot) instead of LDS-DMA
 #ifndef DEC5_RSTAGE
 #define DEC5_RSTAGE 0

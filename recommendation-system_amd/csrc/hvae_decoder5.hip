@@ -8,22 +8,54 @@
 // MFMA waits on (profiles/r02_dec4_ablations.jsonl: the sweep is 18 % faster without the DMA).
 //
 // Here a block is 8 waves, two per SIMD (waves q and q + 4 share one: the workgroup's waves go to the
-// SIMDs in a cyclic order of 4). For q = 0..3, (ug, dh) = (q & 1, q >> 1):
-//   * producer wave q (role 0): U of user group ug's 32 users over all of D (192 VGPRs; DEC5_P32); per
-//     tile: its share of the LDS-DMA pieces of tile t + 2, GEMM1 of tile t + 1 for items 16 dh .. 16 dh + 15
-//     (48 16x16x32 MFMAs, one A read serving both 16-user halves), its 8 exponentials, its P piece -> LDS;
+// SIMDs in a cyclic order of 4). In the bf16 sweep, for q = 0..3 (the fp8 sweep keeps consumers of a user
+// group over a D half: its own comment below):
+//   * producer wave q (role 0), (ug, ih) = (q & 1, q >> 1): U of user group ug's 32 users over all of D
+//     (192 VGPRs; DEC5_P32); per tile: its share of the LDS-DMA pieces of tile t + 2, GEMM1 of tile t + 1 for
+//     items 16 ih .. 16 ih + 15 (48 16x16x32 MFMAs, one A read serving both 16-user halves), its 8
+//     exponentials, its P piece -> LDS;
 //     DEC5_P32=0 (A/B) gives the producer 16 users over both item halves (96 VGPRs, twice the GEMM1 reads);
-//   * consumer wave q + 4 (role 1): O of user group ug over D half dh (192 VGPRs: the file is compiled
-//     with -mllvm -amdgpu-mfma-vgpr-form, so that no AGPR block is allocated beside the producer's
-//     VGPRs and each wave fits the 256 registers of two waves per SIMD); per tile: GEMM2 of tile t
-//     over both item halves (24 32x32x16 MFMAs) with P(t) read back from LDS, and its share of the pieces.
+//   * consumer wave q + 4 (role 1): O of all 64 users of the block over D quarter q, dims 192 q .. 192 q + 191
+//     (192 VGPRs: the file is compiled with -mllvm -amdgpu-mfma-vgpr-form, so that no AGPR block is allocated
+//     beside the producer's VGPRs and each wave fits the 256 registers of two waves per SIMD); per tile: GEMM2
+//     of tile t over both item halves (24 32x32x16 MFMAs = 6 d-blocks x 2 user groups x 2 item halves, each
+//     transposed E^T fragment serving both user groups: 24 ds_read_b64_tr_b16, not 48) with P(t) of both user
+//     groups read back from LDS, and its share of the pieces.
 // The SIMD's two instruction streams interleave in hardware, so one wave's DMA issue, LDS waits and
 // exponentials run under the other's MFMAs. The MFMA work per SIMD and tile is version 4's (1536
-// cycles), as are the LDS image, the DMA piece map, the P layout and the fixed-offset / flag rules. One
-// barrier per tile:
-//   [barrier: tile t + 1 landed, P(t) published, GEMM2(t - 1) done]
-//   producers: DMA of t + 2 into the slot GEMM2(t - 1) freed | GEMM1(t + 1) | softmax | P(t + 1) out
-//   consumers: GEMM2(t) from slot t % 3 and P(t)
+// cycles), as are the LDS image, the piece geometry (48 pieces of 8 items x 64 dims, piece p at p KiB), the P
+// layout and the fixed-offset / flag rules. One barrier per tile:
+//   [L: tile t + 1 landed, P(t) published, GEMM2(t - 1) done]
+//   producers: their pieces of t + 2 into slot (t + 2) % 3 | GEMM1(t + 1) from slot (t + 1) % 3 | softmax |
+//              P(t + 1) out
+//   consumers: GEMM2(t) from slot t % 3 and P(t); after its item half 0, their pieces of t + 3 into slot t % 3
+// Who fills what: waves q and q + 4 issue the 12 pieces of D quarter q (3 columns of 64 dims x 4 row groups of
+// 8 items). Consumer q + 4 is the only GEMM2 reader of that quarter, so it refills DEC5_DMA_B pieces of the
+// quarter's item half 0 (row groups 0, 1) itself, with tile t + 3, right after its 12th MFMA of iteration t --
+// half an iteration before [L] frees the rest of the slot, with 1.5 iterations to land instead of 1. Producer q
+// issues the quarter's other pieces for tile t + 2 after [L], as before. Why this is safe:
+//   (a) A piece is issued only after the MFMAs that consumed every read of its bytes have issued. The consumer's
+//       reads of item half 0 are fragments 0..5; MFMAs 0..11 take them as operands, so each has returned (the
+//       compiler's lgkmcnt wait stands before the MFMA, LDS reads return in order) before the gap after MFMA
+//       11, the first one a piece may stand in (static_assert on DEC5_CDMA_AT); the sched_barrier after every
+//       MFMA keeps the asm statement in its gap. Producer pieces of slot (t + 2) % 3 follow [L](t), which every
+//       wave reaches after GEMM2(t - 1)'s reads (the barrier's lgkmcnt(0)).
+//   (b) No producer reads slot t % 3 during iteration t: GEMM1(t) read it in iteration t - 1 (before [L](t)),
+//       iteration t's GEMM1 reads slot (t + 1) % 3. The prologue's GEMM1(t_beg) reads slot 0 before [P1], the
+//       consumer's first refill of slot 0 follows [L](t_beg); the peeled iterations read as the steady ones do
+//       and issue nothing, and the consumer's prologue pieces of tile t_beg + 2 go into slot 2, which nothing
+//       has read.
+//   (c) Tile t + 3 is first read by GEMM1(t + 3) after [L](t + 2). Before that barrier the consumer waits
+//       vmcnt(DEC5_DMA_B): it has issued iteration t's pieces (tile t + 3), then iteration t + 1's (tile t + 4),
+//       and loads return in order, so at most the later group is still in flight. The third-last iteration
+//       issued nothing after tile t + 2's group and also waits vmcnt(DEC5_DMA_B) (tile t + 1 landed); the last
+//       two wait vmcnt(0). The prologue issues the groups of tiles t_beg, t_beg + 1, t_beg + 2 and waits
+//       vmcnt(DEC5_DMA_B) (vmcnt(0) when the split has no third tile).
+//   (d) Each piece is one asm statement: s_add_u32 m0, s_add_u32 soffset, the load -- the second add stands in
+//       the wait state between a write of M0 and the LDS-DMA load that reads it, wherever the statement is
+//       placed. A wave's first piece of a tile ("fresh") opens with s_nop 4, which covers a descriptor or
+//       offset SGPR written by a v_readfirstlane just before; in the new issue point (an MFMA gap in the
+//       middle of GEMM2) that holds as it did in the first gap.
 // What bounds it (profiles/r03_dec5_ablation_*.jsonl): the E stream. 64 users per 48-KiB tile
 // is 98 GB of L2 -> LDS traffic per Syn-10M sweep; the stream alone, waited per tile as the ring needs,
 // takes 9.4 ms of the 10.1-10.4, while the MFMAs alone take 6.9.
@@ -56,19 +88,14 @@ __device__ unsigned long long dec5_tm[2048 * 8];
 #ifndef DEC5_GLDS
 #define DEC5_GLDS 0
 #endif
-#ifndef DEC5_CRSTAGE
-#define DEC5_CRSTAGE 0
-#endif
 
 template <bool WITH_O>
 __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, int64_t ldu,
                                                    const bf16_t* __restrict__ E, const float* __restrict__ e_maxnorm,
                                                    int64_t nb, int64_t N, int splits, int64_t tiles_per_split,
                                                    Out out) {
-  constexpr int DW = D / 2;      // GEMM2: dims owned by one consumer wave
-  constexpr int DB = DW / 32;    // GEMM2 d-blocks (12)
   constexpr int KS = D / 32;     // GEMM1 k-steps (24)
-  constexpr int PW = 12;         // 1-KiB LDS-DMA pieces per (ug, dh) per tile
+  constexpr int PW = 12;         // 1-KiB LDS-DMA pieces per D quarter (waves q and q + 4) per tile
   constexpr int PB = DEC5_DMA_B;
   constexpr int PA = PW - PB;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -104,7 +131,6 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   const int64_t ntiles = (N + kTI - 1) / kTI;
   const int64_t t_beg = (int64_t)split * tiles_per_split;
   const int64_t t_end = min(ntiles, t_beg + tiles_per_split);
-  const int dbase = dh * DW;
 
   // LDS-DMA into version 2's image (version 3's pieces): piece p = q * 12 + i
   int vlane[2];
@@ -115,7 +141,14 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   }
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(E), (short)0, (int)(N * D * 2), 0x00020000);
-  const uint32_t ring0 = lds_addr(lds) + (uint32_t)(q * PW * 1024);
+  const uint32_t ring0 = lds_addr(lds);
+  // Piece n (0..11) of D quarter q, the 12 pieces that waves q and q + 4 issue: row group n / 3 (8 items), 64-dim
+  // column 3 q + n % 3 of the tile's 12. The consumer takes n < PB (item half 0: row groups 0 and 1, which its
+  // first 12 MFMAs consume), the producer n >= PB. Returns the piece's number p in the image (LDS offset p KiB)
+  auto qpiece = [&](int n) {
+    const int j = 3 * q + n % 3;
+    return ((j >> 1) << 3) + ((n / 3) << 1) + (j & 1);
+  };
 #ifndef DEC5_DMA_NT
 #define DEC5_DMA_NT 0  // A/B: non-temporal cache policy on the LDS-DMA pieces
 #endif
@@ -128,42 +161,43 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   // piece's own image offset depends on the wave (q) but not on the tile: the compiler hoists it out of the loops
   // into an SGPR. Product form: M0 and the load's soffset cost one scalar add each, and the second add stands in the
   // wait state an LDS-DMA load needs after a write of M0. Every form names m0 as clobbered
-  auto dma_piece = [&](uint32_t lb, uint32_t soff, int i, bool fresh) {
-    if ((DEC5_ABL & 256) && (i & 1)) return;
-    const int p = q * PW + i;
+  auto dma_piece = [&](uint32_t lb, uint32_t soff, int n, bool fresh) {
+    if ((DEC5_ABL & 256) && (n & 1)) return;
+    const int p = qpiece(n);
     const uint32_t po = (uint32_t)(8 * ((p >> 1) & 3) * (D * 2) + 256 * (p >> 3) + 128 * (p & 1));
-    const int vo = ((p >> 1) & 1) ? vlane[1] : vlane[0];
+    const uint32_t lo = (uint32_t)(p * 1024);
+    const int vo = ((n / 3) & 1) ? vlane[1] : vlane[0];
 #if DEC5_GLDS
     const unsigned char* src = reinterpret_cast<const unsigned char*>(E) + (soff + po);  // wave-uniform: an SGPR pair
     if (fresh)
       asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" DEC5_POL
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(src) : "memory", "m0");
+                   :: "s"(lb + lo), "v"(vo), "s"(src) : "memory", "m0");
     else
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" DEC5_POL
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(src) : "memory", "m0");
-#elif DEC5_ROT  // i is not a compile-time constant
+                   :: "s"(lb + lo), "v"(vo), "s"(src) : "memory", "m0");
+#elif DEC5_ROT  // n is not a compile-time constant
     if (fresh)
       asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" DEC5_POL " lds"
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(rsrc), "s"(soff + po) : "memory", "m0");
+                   :: "s"(lb + lo), "v"(vo), "s"(rsrc), "s"(soff + po) : "memory", "m0");
     else
       asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen" DEC5_POL " lds"
-                   :: "s"(lb + (uint32_t)(i * 1024)), "v"(vo), "s"(rsrc), "s"(soff + po) : "memory", "m0");
+                   :: "s"(lb + lo), "v"(vo), "s"(rsrc), "s"(soff + po) : "memory", "m0");
 #else
     uint32_t so;
     if (fresh)
       asm volatile("s_nop 4\n\ts_add_u32 m0, %2, %3\n\ts_add_u32 %0, %4, %5\n\t"
                    "buffer_load_dwordx4 %1, %6, %0 offen" DEC5_POL " lds"
-                   : "=&s"(so) : "v"(vo), "s"(lb), "i"(i * 1024), "s"(soff), "s"(po), "s"(rsrc)
+                   : "=&s"(so) : "v"(vo), "s"(lb), "s"(lo), "s"(soff), "s"(po), "s"(rsrc)
                    : "memory", "m0", "scc");
     else
       asm volatile("s_add_u32 m0, %2, %3\n\ts_add_u32 %0, %4, %5\n\t"
                    "buffer_load_dwordx4 %1, %6, %0 offen" DEC5_POL " lds"
-                   : "=&s"(so) : "v"(vo), "s"(lb), "i"(i * 1024), "s"(soff), "s"(po), "s"(rsrc)
+                   : "=&s"(so) : "v"(vo), "s"(lb), "s"(lo), "s"(soff), "s"(po), "s"(rsrc)
                    : "memory", "m0", "scc");
 #endif
   };
-  auto issue_piece = [&](uint32_t soff, int slot_i, int i, bool fresh) {
-    dma_piece(ring0 + (uint32_t)(slot_i * TB), soff, i, fresh);
+  auto issue_piece = [&](uint32_t soff, int slot_i, int n, bool fresh) {
+    dma_piece(ring0 + (uint32_t)(slot_i * TB), soff, n, fresh);
   };
   auto tile_soff = [&](int64_t t) {
     return (uint32_t)__builtin_amdgcn_readfirstlane((int)(t * (int64_t)(kTI * D * 2)));
@@ -181,8 +215,9 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   auto prot = [&](int i, int n) { return DEC5_ROT ? (i + rot) % n : i; };
   // The tile loops run on 32-bit scalars: the split's tile count, the image offset of the tile the DMA fetches
   // (running; the image is below 2 GiB, the buffer resource's rule) and the ring's slot offsets rotating through
-  // three SGPRs. Their last two iterations, which fetch nothing, are peeled off, so the steady-state bodies issue
-  // their pieces unconditionally; only the sweep's last tile, reached in the peeled part, can need the tail mask
+  // three SGPRs. Their last iterations, which fetch nothing (two for the producers, who fetch tile t + 2; three for
+  // the consumers, who fetch tile t + 3), are peeled off, so the steady-state bodies issue their pieces
+  // unconditionally; only the sweep's last tile, reached in the peeled part, can need the tail mask
   constexpr uint32_t kTileStep = (uint32_t)(kTI * D * 2);
   constexpr uint32_t kPPar = 2 * 32 * PST;  // bytes between the two parities of pbuf
   const int n_tiles = __builtin_amdgcn_readfirstlane(t_beg < t_end ? (int)(t_end - t_beg) : 0);
@@ -291,10 +326,10 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
     };
     if (t_beg < t_end) {
 #pragma unroll
-      for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg), 0, i, i == 0);
+      for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg), 0, PB + i, i == 0);
       if (t_beg + 1 < t_end) {
 #pragma unroll
-        for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+        for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg + 1), 1, PB + i, false);
       }
       wait_vmcnt<0>();
     }
@@ -338,7 +373,7 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
           const int kk = ks - DEC5_PDMA_AT;
           if constexpr (decltype(dma)::value)
             if (!(DEC5_ABL & 1) && kk >= 0 && kk % DEC5_DMA_STRIDE == 0 && kk / DEC5_DMA_STRIDE < PA)
-              dma_piece(lb_dma, soff_dma, prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
+              dma_piece(lb_dma, soff_dma, PB + prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
         });
         DEC5_T(tm3 = __builtin_amdgcn_s_memtime();)
         if constexpr (decltype(tail)::value)
@@ -478,21 +513,21 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
 #if DEC5_RSTAGE
     uint4 stg[PA > 0 ? PA : 1];
     auto rs_load = [&](int64_t tt, int i) {
-      const int p = q * PW + i;
+      const int p = qpiece(PB + i);
       const uint32_t so = tile_soff(tt) + (uint32_t)(8 * ((p >> 1) & 3) * (D * 2) + 256 * (p >> 3) + 128 * (p & 1));
       const int vo = ((p >> 1) & 1) ? vlane[1] : vlane[0];
       stg[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, (int)so, 0));
     };
     auto rs_write = [&](int slot_i, int i) {
-      *reinterpret_cast<uint4*>(lds + slot_i * TB + q * PW * 1024 + i * 1024 + lane * 16) = stg[i];
+      *reinterpret_cast<uint4*>(lds + slot_i * TB + qpiece(PB + i) * 1024 + lane * 16) = stg[i];
     };
 #endif
     if (t_beg < t_end) {
 #pragma unroll
-      for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg), 0, i, i == 0);
+      for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg), 0, PB + i, i == 0);
       if (t_beg + 1 < t_end) {
 #pragma unroll
-        for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+        for (int i = 0; i < PA; ++i) issue_piece(tile_soff(t_beg + 1), 1, PB + i, false);
       }
       wait_vmcnt<0>();
 #if DEC5_RSTAGE
@@ -535,11 +570,11 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
 #if DEC5_DMA_BURST
           if (dma && ks == DEC5_PDMA_AT) {
 #pragma unroll
-            for (int i = 0; i < PA; ++i) issue_piece(soff_dma, s_dma, i, i == 0);
+            for (int i = 0; i < PA; ++i) issue_piece(soff_dma, s_dma, PB + i, i == 0);
           }
 #else
           const int kk = ks - DEC5_PDMA_AT;
-          if (dma && kk >= 0 && kk % DEC5_DMA_STRIDE == 0 && kk / DEC5_DMA_STRIDE < PA) issue_piece(soff_dma, s_dma, prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
+          if (dma && kk >= 0 && kk % DEC5_DMA_STRIDE == 0 && kk / DEC5_DMA_STRIDE < PA) issue_piece(soff_dma, s_dma, PB + prot(kk / DEC5_DMA_STRIDE, PA), kk == 0);
 #endif
         });
 #endif
@@ -561,154 +596,171 @@ __global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, 
   }
 
   // -------------------------------------------------------------------- consumer ---
-  // GEMM2 (version 3's reads): O^T[DW][32 users] += E^T P^T over k-steps 0 (items 0..15) and 1 (16..31)
-  const int64_t user = u0 + col;
-  const bool wave_active = u0 < nb;
+  // GEMM2 (version 3's reads): consumer q owns O^T[D quarter q][64 users]: global d-blocks 6 q .. 6 q + 5 of 32 dims,
+  // user blocks ub = 0, 1 (the two user groups). Per tile and item half kh: one E^T fragment per d-block (two
+  // transposed reads) serves the MFMAs of both user blocks -- 24 MFMAs from 24 reads. o[db][ub] takes item half 0,
+  // then item half 1, with the operands the (ug, dh) consumers gave it: no sum is reordered.
+  constexpr int QB = D / 4 / 32;  // d-blocks per quarter (6)
+  constexpr int NM = 4 * QB;      // MFMAs per tile (24)
+  static_assert(PB <= 6, "the consumer's pieces are item half 0's: 3 columns x 2 row groups");
+  static_assert(DEC5_CDMA_AT >= 0 && 2 * QB - 1 + DEC5_CDMA_AT + (PB > 0 ? PB - 1 : 0) * DEC5_DMA_STRIDE < NM,
+                "the consumer's pieces go into the MFMA gaps after item half 0");
+  const int64_t user0 = (int64_t)ublk * 64 + col;  // user block 1: + 32
   const int g1 = (lane >> 4) & 1, qq = (lane >> 2) & 3, pp = lane & 3;
-  const int cseg = (dbase / 128) << 13;
-  auto dboff = [](int db) { return ((db >> 2) << 13) + ((db & 3) << 9); };
-  const int laneT0 = ((4 * h + qq) << 6) + (((2 * g1 + (pp >> 1)) ^ ((0 + h) & 3)) << 4) + 8 * (pp & 1);
-  const int laneT1 = ((4 * h + qq) << 6) + (((2 * g1 + (pp >> 1)) ^ ((2 + h) & 3)) << 4) + 8 * (pp & 1);
-  f32x16 o[WITH_O ? DB : 1];
+  // The quarter's three 64-dim columns j = 3 q + {0, 1, 2} lie at ((j >> 1) << 13) + ((j & 1) << 10) of the image,
+  // i.e. d-block 6 q + db at ((gdb >> 2) << 13) + ((gdb & 3) << 9): the first at cb0, the third 8 KiB on, the
+  // second 1 KiB (q even) or 7 KiB (q odd) on -- two bases per lane map, every other term an immediate
+  const int cb0 = (((3 * q) >> 1) << 13) + (((3 * q) & 1) << 10);
+  const int cmid = (q & 1) ? 7168 : 1024;
+  const int laneT0 = ((4 * h + qq) << 6) + (((2 * g1 + (pp >> 1)) ^ ((0 + h) & 3)) << 4) + 8 * (pp & 1) + cb0;
+  const int laneT1 = ((4 * h + qq) << 6) + (((2 * g1 + (pp >> 1)) ^ ((2 + h) & 3)) << 4) + 8 * (pp & 1) + cb0;
+  f32x16 o[WITH_O ? QB : 1][2];
 #pragma unroll
-  for (int d = 0; d < (WITH_O ? DB : 1); ++d)
+  for (int d = 0; d < (WITH_O ? QB : 1); ++d)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
+    for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) o[d][ub][r] = 0.f;
   constexpr int BH = DEC5_G2_AHEAD;
-  auto rdT = [&](const unsigned char* buf, int i) {
-    const int kh = i / DB, db = i % DB;
-    const unsigned char* tt = buf + cseg + (kh << 12);
-    auto* p0 = (__attribute__((address_space(3))) s16x4*)(void*)(tt + laneT0 + dboff(db));
-    auto* p1 = (__attribute__((address_space(3))) s16x4*)(void*)(tt + laneT1 + (1 << 11) + dboff(db));
+  // fragment r = (item half r / QB, d-block r % QB) of the tile at buf: rows 16 kh .. 16 kh + 15 (row groups 2 kh
+  // and 2 kh + 1), 32 dims
+  auto rdT = [&](const unsigned char* buf, int r) {
+    const int kh = r / QB, db = r % QB;
+    const unsigned char* tt = buf + (kh << 12) + ((db & 1) << 9) + ((db >> 1) == 2 ? 8192 : 0);
+    const int mid = (db >> 1) == 1 ? cmid : 0;
+    auto* p0 = (__attribute__((address_space(3))) s16x4*)(void*)(tt + (laneT0 + mid));
+    auto* p1 = (__attribute__((address_space(3))) s16x4*)(void*)(tt + (laneT1 + mid) + (1 << 11));
     return std::array<s16x4, 2>{__builtin_amdgcn_ds_read_tr16_b64_v4i16(p0), __builtin_amdgcn_ds_read_tr16_b64_v4i16(p1)};
   };
-  auto gemm2 = [&](const unsigned char* buf, const uint4& pf0, const uint4& pf1, auto&& fill) {
+  // pf[ub][kh]: P(t) of user block ub, item half kh; fill(i) stands in the gap after MFMA i
+  auto gemm2 = [&](const unsigned char* buf, const uint4 (&pf)[2][2], auto&& fill) {
     if constexpr (WITH_O) {
       std::array<s16x4, 2> n[BH];
 #pragma unroll
       for (int j = 0; j < BH; ++j) n[j] = rdT(buf, j);
 #pragma unroll
-      for (int i = 0; i < 2 * DB; ++i) {
-        const std::array<s16x4, 2> c = n[i % BH];
-        if (!(DEC5_ABL & 16) && i + BH < 2 * DB) n[i % BH] = rdT(buf, i + BH);
+      for (int r = 0; r < 2 * QB; ++r) {
+        const std::array<s16x4, 2> c = n[r % BH];
+        if (!(DEC5_ABL & 16) && r + BH < 2 * QB) n[r % BH] = rdT(buf, r + BH);
         const s16x8 a = {c[0][0], c[0][1], c[0][2], c[0][3], c[1][0], c[1][1], c[1][2], c[1][3]};
-        if (!(DEC5_ABL & 64))
-          o[i % DB] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
-                                                             __builtin_bit_cast(bf16x8, i < DB ? pf0 : pf1), o[i % DB],
-                                                             0, 0, 0);
-        else
-          o[i % DB][0] += (float)__builtin_bit_cast(bf16x8, a)[0];
-        fill(i);
-        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int ub = 0; ub < 2; ++ub) {
+          if (!(DEC5_ABL & 64))
+            o[r % QB][ub] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a),
+                                                                   __builtin_bit_cast(bf16x8, pf[ub][r / QB]),
+                                                                   o[r % QB][ub], 0, 0, 0);
+          else
+            o[r % QB][ub][0] += (float)__builtin_bit_cast(bf16x8, a)[0];
+          fill(2 * r + ub);
+          __builtin_amdgcn_sched_barrier(0);
+        }
       }
     } else {
 #pragma unroll
-      for (int i = 0; i < 2 * DB; ++i) fill(i);
+      for (int i = 0; i < NM; ++i) fill(i);
     }
   };
   if constexpr (PB > 0) {
     if (t_beg < t_end) {
 #pragma unroll
-      for (int i = PA; i < PW; ++i) issue_piece(tile_soff(t_beg), 0, i, i == PA);
+      for (int k = 0; k < PB; ++k) issue_piece(tile_soff(t_beg), 0, k, k == 0);
       if (t_beg + 1 < t_end) {
 #pragma unroll
-        for (int i = PA; i < PW; ++i) issue_piece(tile_soff(t_beg + 1), 1, i, false);
+        for (int k = 0; k < PB; ++k) issue_piece(tile_soff(t_beg + 1), 1, k, false);
       }
-      wait_vmcnt<0>();
+      if (t_beg + 2 < t_end) {  // its share of the third tile: in flight across [P0] .. the [L] of iteration 1
+#pragma unroll
+        for (int k = 0; k < PB; ++k) issue_piece(tile_soff(t_beg + 2), 2, k, false);
+        wait_vmcnt<PB>();
+      } else {
+        wait_vmcnt<0>();
+      }
     }
   }
-#if DEC5_CRSTAGE
-  // DEC5_CRSTAGE=1 (A/B): the consumer's PB pieces of each tile through registers instead of LDS-DMA -- loaded by
-  // buffer_load_dwordx4 in GEMM2(t)'s first gaps (tile t + 2; past the split the loads re-read tile t and are not
-  // written), written by ds_write_b128 into the same image bytes before the next iteration's barrier
-  uint4 cst[PB > 0 ? PB : 1];
-  auto c_load = [&](uint32_t soff, int k) {
-    const int p = q * PW + PA + k;
-    const uint32_t so = soff + (uint32_t)(8 * ((p >> 1) & 3) * (D * 2) + 256 * (p >> 3) + 128 * (p & 1));
-    const int vo = ((p >> 1) & 1) ? vlane[1] : vlane[0];
-    cst[k] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, vo, (int)so, 0));
-  };
-  auto c_write = [&](uint32_t slot_off) {
-#pragma unroll
-    for (int k = 0; k < PB; ++k)
-      *reinterpret_cast<uint4*>(lds + slot_off + (q * PW + PA + k) * 1024 + lane * 16) = cst[k];
-  };
-#endif
   barrier();  // [P0]
   if (DEC5_P32) barrier();  // [PX]
   barrier();  // [P1]
-  // iteration li (tile t = t_beg + li): GEMM2 reads slot li % 3, the DMA fills slot (li + 2) % 3 with tile t + 2
-  uint32_t o_cur = 0, o_nxt = TB, o_dma = 2 * TB, soff_dma = tile_soff(t_beg + 2);
+  // iteration li (tile t = t_beg + li): GEMM2 reads slot li % 3; once its item half 0 is consumed, the consumer's
+  // own pieces of that slot are refilled with tile t + 3
+  uint32_t o_cur = 0, o_nxt = TB, o_aft = 2 * TB, soff_dma = tile_soff(t_beg + 3);
   uint32_t p_off = 0;  // byte offset of P(t)'s parity
   int rem = n_tiles;
-  // P(t) in GEMM2's B layout: user col, positions 8 h .. 8 h + 7 of k-steps 0 and 1
-  const unsigned char* const pr0 = p_row(0, col) + 16 * h;
-  auto iter = [&](auto dma_t) {
-    constexpr bool dma = decltype(dma_t)::value && !(DEC5_ABL & 1);  // tile t + 2 exists and is fetched
+  // P(t) in GEMM2's B layout: user col of block ub, positions 8 h .. 8 h + 7 of k-steps 0 and 1
+  const unsigned char* const pr0 = pbuf + col * PST + 16 * h;
+  // dma: tile t + 3 exists and is fetched; flight: how many of the wave's pieces may still be in flight at [L]
+  // (the ones issued in the previous iteration, which carry tile t + 2)
+  auto iter = [&](auto dma_t, auto flight_t) {
+    constexpr bool dma = decltype(dma_t)::value && !(DEC5_ABL & 1);
     DEC5_T(const unsigned long long tm0 = __builtin_amdgcn_s_memtime();)
-    if constexpr (PB > 0) if (!(DEC5_ABL & (1 | 128))) wait_vmcnt<0>();
-#if DEC5_CRSTAGE
-    if (rem < n_tiles && rem > 1) c_write(o_nxt);  // tile t + 1, loaded in the previous iteration
-#endif
+    if constexpr (PB > 0) if (!(DEC5_ABL & (1 | 128))) wait_vmcnt<decltype(flight_t)::value>();
     DEC5_T(const unsigned long long tm1 = __builtin_amdgcn_s_memtime();)
     if (!(DEC5_ABL & 2)) barrier();  // [L]
     DEC5_T(const unsigned long long tm2 = __builtin_amdgcn_s_memtime();)
-    const uint4 pf0 = *reinterpret_cast<const uint4*>(pr0 + p_off);
-    const uint4 pf1 = *reinterpret_cast<const uint4*>(pr0 + p_off + 32);
-    const uint32_t lb_dma = ring0 + o_dma;
-#if DEC5_CRSTAGE
-    const uint32_t soff_ld = rem > 2 ? soff_dma : soff_dma - 2 * kTileStep;
-#endif
-    gemm2(lds + o_cur, pf0, pf1, [&](int i) {
-      const int ii = i - DEC5_CDMA_AT;
-#if DEC5_CRSTAGE
-      if constexpr (PB > 0)
-        if (ii >= 0 && ii < PB) c_load(soff_ld, ii);
-#elif DEC5_DMA_BURST
-      if constexpr (PB > 0 && dma)
+    uint4 pf[2][2];
+#pragma unroll
+    for (int ub = 0; ub < 2; ++ub)
+#pragma unroll
+      for (int kh = 0; kh < 2; ++kh)
+        pf[ub][kh] = *reinterpret_cast<const uint4*>(pr0 + p_off + ub * 32 * PST + 32 * kh);
+    const uint32_t lb_dma = ring0 + o_cur;
+    gemm2(lds + o_cur, pf, [&](int i) {
+      const int ii = i - (2 * QB - 1) - DEC5_CDMA_AT;  // gap 0: after the last MFMA of item half 0
+      if constexpr (PB > 0 && dma) {
+#if DEC5_DMA_BURST
         if (ii == 0) {
 #pragma unroll
-          for (int k = 0; k < PB; ++k) dma_piece(lb_dma, soff_dma, PA + k, k == 0);
+          for (int k = 0; k < PB; ++k) dma_piece(lb_dma, soff_dma, k, k == 0);
         }
 #else
-      if constexpr (PB > 0 && dma)
         if (ii >= 0 && ii % DEC5_DMA_STRIDE == 0 && ii / DEC5_DMA_STRIDE < PB)
-          dma_piece(lb_dma, soff_dma, PA + prot(ii / DEC5_DMA_STRIDE, PB), ii == 0);
+          dma_piece(lb_dma, soff_dma, prot(ii / DEC5_DMA_STRIDE, PB), ii == 0);
 #endif
+      }
     });
     const uint32_t o = o_cur;
-    o_cur = o_nxt; o_nxt = o_dma; o_dma = o;
+    o_cur = o_nxt; o_nxt = o_aft; o_aft = o;
     soff_dma += kTileStep;
     p_off ^= kPPar;
     DEC5_T(const unsigned long long tm3 = __builtin_amdgcn_s_memtime(); tacc[0] += tm1 - tm0; tacc[1] += tm2 - tm1;
            tacc[2] += tm3 - tm2; ++ntl;)
   };
-  // DEC5_BFREE (A/B): the last two iterations issue pieces too (past the split they fill the free slot)
-  for (; rem > (DEC5_BFREE ? 0 : 2); --rem) iter(std::true_type{});
-  for (; rem > 0; --rem) iter(std::false_type{});
+  constexpr std::integral_constant<int, PB> one_tile{};
+  constexpr std::integral_constant<int, 0> none{};
+  // The last three iterations fetch nothing (tiles t + 3 are past the split) and are peeled off. Third-last: tile
+  // t + 2's pieces may still fly, tile t + 1's must have landed -> vmcnt(PB); the last two wait for everything.
+  // DEC5_BFREE (A/B): every iteration issues (past the split into its own region, which nobody reads again)
+  for (; rem > (DEC5_BFREE ? 0 : 3); --rem) iter(std::true_type{}, one_tile);
+  if (rem == 3) { iter(std::false_type{}, one_tile); --rem; }
+  for (; rem > 0; --rem) iter(std::false_type{}, none);
   if constexpr (PB > 0) wait_vmcnt<0>();
   if (DEC5_P32) barrier();  // [PE0]
   barrier();  // [E0]
   barrier();  // [E1] producers' (l, m) published
   DEC5_T(tm_store();)
-  if (!wave_active || t_beg >= t_end || user >= nb) return;
-  const float ltot = xm[ug * 64 + col], mu = xm[ug * 64 + 32 + col];
-  if (h == 0 && dh == 0) out.flag[out.direct ? user : (int64_t)split * nb + user] = !(ltot >= kMinL);
-  const int64_t row = out.direct ? user : (int64_t)split * nb + user;
-  if (h == 0 && dh == 0) {
-    if (out.direct) out.lse[user] = mu + logf(ltot);
-    else { out.m[row] = mu; out.l[row] = ltot; }
-  }
-  if (WITH_O) {
-    const float sc = out.direct ? 1.0f / ltot : 1.0f;
+  if (t_beg >= t_end) return;
 #pragma unroll
-    for (int d = 0; d < (WITH_O ? DB : 1); ++d)
+  for (int ub = 0; ub < 2; ++ub) {
+    const int64_t user = user0 + 32 * ub;
+    if (user >= nb) continue;
+    const float ltot = xm[ub * 64 + col], mu = xm[ub * 64 + 32 + col];
+    const int64_t row = out.direct ? user : (int64_t)split * nb + user;
+    if (h == 0 && q == 0) {  // once per user
+      out.flag[row] = !(ltot >= kMinL);
+      if (out.direct) out.lse[user] = mu + logf(ltot);
+      else { out.m[row] = mu; out.l[row] = ltot; }
+    }
+    if (WITH_O) {
+      const float sc = out.direct ? 1.0f / ltot : 1.0f;
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int dd = dbase + 32 * d + 8 * g4 + 4 * h;
-        *reinterpret_cast<float4*>(out.O + row * D + dd) =
-            make_float4(o[d][4 * g4] * sc, o[d][4 * g4 + 1] * sc, o[d][4 * g4 + 2] * sc, o[d][4 * g4 + 3] * sc);
-      }
+      for (int d = 0; d < (WITH_O ? QB : 1); ++d)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int dd = q * (D / 4) + 32 * d + 8 * g4 + 4 * h;
+          *reinterpret_cast<float4*>(out.O + row * D + dd) =
+              make_float4(o[d][ub][4 * g4] * sc, o[d][ub][4 * g4 + 1] * sc, o[d][ub][4 * g4 + 2] * sc,
+                          o[d][ub][4 * g4 + 3] * sc);
+        }
+    }
   }
 }
 
@@ -1070,7 +1122,7 @@ __global__ void __launch_bounds__(512) k_dec5_f8(const float* __restrict__ U, in
     }
   }
 #if DEC5F8_CRSTAGE
-  // DEC5F8_CRSTAGE=1 (A/B; bf16: DEC5_CRSTAGE): the consumer's PB pieces through registers -- buffer_load_dwordx4 in
+  // DEC5F8_CRSTAGE=1 (A/B): the consumer's PB pieces through registers -- buffer_load_dwordx4 in
   // GEMM2(t)'s first gaps (tile t + 2), ds_write_b128 into the same image bytes before the next barrier
   uint4 cst[PB > 0 ? PB : 1];
   auto c_load = [&](uint32_t soff, int k) {
