@@ -770,6 +770,41 @@ int hvae_lgcn_bpr(const float* F, int64_t n_users, int64_t n_items, int64_t d, c
                   int64_t n_seg, double reg, float* g, float* loss_out, double* loss_accum, void* ws,
                   size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------- SVD (K19) -- */
+/* The SVD baseline (SVDRecommender, src/ml/baseline.py:102-118: scikit-learn's randomized TruncatedSVD) as a
+ * subspace iteration over the interaction matrix: tall-skinny linear algebra in fp64. A tall matrix is
+ * [n, HVAE_SVD_LD] doubles, row-major, with W live columns (1 <= W <= HVAE_SVD_LD; W = n_components + 10 in the
+ * baseline); the columns from W up are written as zeros and never read as data. A small matrix is
+ * [HVAE_SVD_LD, HVAE_SVD_LD] doubles, row-major. No atomics; every sum has one fixed order that depends on the
+ * shapes only, so two calls give the same bits.
+ *
+ * hvae_svd_spmm: out[r, :] = sum_e (double)vals[e] * X[idx[e], :] over the entries e in [ptr[r], ptr[r + 1]) of a
+ * compressed matrix with n_rows rows and n_cols columns (ptr int64 [n_rows + 1], idx int32, vals fp32, duplicates
+ * summed): A X from the CSR of A, A^T X from its CSC. X is [n_cols, HVAE_SVD_LD], out [n_rows, HVAE_SVD_LD]; out
+ * may not alias X. An empty row gives exact zeros; an index outside [0, n_cols) gives NaN in its row, never a read
+ * out of bounds. A wave owns a row (lane = column) and walks its entries in storage order, 64 at a time, over four
+ * accumulators merged (a0 + a1) + (a2 + a3); a row of more than 256 entries is cut into four contiguous quarters
+ * over the waves of its block, merged ((q0 + q1) + q2) + q3. */
+#define HVAE_SVD_LD 64
+int hvae_svd_spmm(const int64_t* ptr, const int32_t* idx, const float* vals, int64_t n_rows, int64_t n_cols,
+                  const double* X, double* out, int64_t W, void* stream);
+/* G [HVAE_SVD_LD, HVAE_SVD_LD] = Y^T Y over Y [n, HVAE_SVD_LD], zero outside W x W and exactly symmetric: per-block
+ * partial Gram matrices over fixed row chunks (into ws, hvae_svd_gram_workspace(n) bytes, 8-byte aligned), then
+ * their sum in block order. */
+size_t hvae_svd_gram_workspace(int64_t n);
+int hvae_svd_gram(const double* Y, int64_t n, int64_t W, double* G, void* ws, size_t ws_bytes, void* stream);
+/* G[:W, :W] = R^T R (Cholesky, one block) and Rinv = R^-1, upper triangular, zero outside W x W. A pivot that is
+ * NaN or not positive -- at or below HVAE_SVD_LD * 2^-53 times its own diagonal entry of G, the rounding error it
+ * carries -- sets the sticky device flag *flag = 1 (G is then not positive definite to working precision: Y's
+ * columns are linearly dependent) and the result holds NaN or noise. The kernel never clears the flag and nothing
+ * on the host waits for it. Rinv may not alias G. */
+int hvae_svd_chol_inv(const double* G, int64_t W, double* Rinv, int32_t* flag, void* stream);
+/* out[r, :W_out] = Y[r, :W] . T[:W, :W_out] for the n rows of Y, zeros from W_out up; T a small matrix. A row
+ * depends on itself only and is read whole before it is written: out may be Y. CholeskyQR2, the orthonormalisation
+ * of Y's columns, is gram -> chol_inv -> apply(Y, Rinv) in place, twice. */
+int hvae_svd_apply(const double* Y, int64_t n, int64_t W, const double* T, int64_t W_out, double* out,
+                   void* stream);
+
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and
  * released by hvae_host_csr_free. */

@@ -138,6 +138,7 @@ class LgcnGraph(C.Structure):  # hvae_lgcn_graph
 
 
 LGCN_MAX_BATCH = 1024  # include/hvae.h HVAE_LGCN_MAX_BATCH
+SVD_LD = 64            # include/hvae.h HVAE_SVD_LD
 
 P = C.POINTER
 # name ->(restype, argtypes); mirrors include/hvae.h one to one.
@@ -227,6 +228,11 @@ SIGNATURES = {
     "hvae_lgcn_propagate": (cint, [P(LgcnGraph), i64, vp, vp, vp, f32, vp]),
     "hvae_lgcn_bpr_workspace": (sz, [i64]),
     "hvae_lgcn_bpr": (cint, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, i64, f64, vp, vp, vp, vp, sz, vp]),
+    "hvae_svd_spmm": (cint, [vp, vp, vp, i64, i64, vp, vp, i64, vp]),
+    "hvae_svd_gram_workspace": (sz, [i64]),
+    "hvae_svd_gram": (cint, [vp, i64, i64, vp, vp, sz, vp]),
+    "hvae_svd_chol_inv": (cint, [vp, i64, vp, vp, vp]),
+    "hvae_svd_apply": (cint, [vp, i64, i64, vp, i64, vp, vp]),
     "hvae_cast_bf16": (cint, [vp, vp, i64, vp]),
     "hvae_negatives_legacy": (cint, [vp, vp, vp, i64, vp, i64, vp, vp, i64, C.c_int32, vp, vp]),
     "hvae_read_interactions": (cint, [C.c_char_p, C.c_char_p, i64, i64, C.c_char_p, i64, i64, cint,

@@ -759,3 +759,122 @@ def lgcn_bpr(F: torch.Tensor, n_users: int, users: torch.Tensor, pos: torch.Tens
                               ptr(seg_off), int(n_seg), float(reg), ptr(g), ptr(loss), ptr(loss_accum), ptr(ws),
                               ws.numel(), stream_of(F)), "hvae_lgcn_bpr")
     return loss, g
+
+
+# ---------------------------------------------------------------------- SVD --
+SVD_LD = _lib.SVD_LD  # the fixed leading dimension of a tall fp64 matrix (include/hvae.h HVAE_SVD_LD)
+
+
+def _svd_width(what: str, W: int) -> int:
+    if not 1 <= int(W) <= SVD_LD:
+        raise ValueError(f"{what}: W = {W} is not served; served: 1 to {SVD_LD} live columns")
+    return int(W)
+
+
+def _svd_tall(what: str, name: str, t: torch.Tensor, n: int | None = None):
+    require_hip(t)
+    if t.dtype != torch.float64:
+        raise ValueError(f"{what}: {name} must be float64, got {t.dtype}")
+    if t.dim() != 2 or t.shape[1] != SVD_LD or not t.is_contiguous() or (n is not None and t.shape[0] != n) \
+            or t.shape[0] < 1:
+        raise ValueError(f"{what}: {name} must be a contiguous [{'n' if n is None else n}, {SVD_LD}] matrix (leading "
+                         f"dimension {SVD_LD}), got {tuple(t.shape)} with strides {tuple(t.stride())}")
+
+
+def _svd_alias(what: str, a: torch.Tensor, b: torch.Tensor, names: str):
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    if a0 < b0 + b.numel() * b.element_size() and b0 < a0 + a.numel() * a.element_size():
+        raise ValueError(f"{what}: {names} may not alias (their memory overlaps)")
+
+
+def svd_tall(n: int, device, src=None) -> torch.Tensor:
+    """A zeroed [n, SVD_LD] fp64 device matrix; with src (a host [n, W] array) its first W columns filled."""
+    t = torch.zeros(n, SVD_LD, dtype=torch.float64, device=device)
+    if src is not None:
+        t[:, :src.shape[1]] = torch.as_tensor(src, dtype=torch.float64).to(device)
+    return t
+
+
+def svd_spmm(m, X: torch.Tensor, W: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out [n_rows, 64] = m X in fp64 over the compressed image m (hvae_svd_spmm): a Csr gives A X (X [n_items, 64]),
+    a Csc gives A^T X (X [n_users, 64]). out may not alias X."""
+    if isinstance(m, Csr):
+        if m.rows is not None:
+            raise ValueError("svd_spmm: the CSR must hold the whole matrix, not a batch view")
+        p, idx, vals, n_rows, n_cols = m.row_ptr, m.col_idx, m.vals, m.nb, m.n_items
+    elif isinstance(m, Csc):
+        p, idx, vals, n_rows, n_cols = m.col_ptr, m.row_idx, m.vals, m.n_items, m.n_users
+    else:
+        raise TypeError("svd_spmm takes an ops.Csr or an ops.Csc")
+    W = _svd_width("svd_spmm", W)
+    _svd_tall("svd_spmm", "X", X, n_cols)
+    if out is None:
+        out = torch.empty(n_rows, SVD_LD, dtype=torch.float64, device=X.device)
+    require_hip(out)
+    _svd_alias("svd_spmm", X, out, "X and out")
+    _svd_tall("svd_spmm", "out", out, n_rows)
+    if p.numel() != n_rows + 1 or idx.numel() != vals.numel():
+        raise ValueError("svd_spmm: the compressed image is inconsistent")
+    if idx.numel() == 0:
+        return out.zero_()
+    check(lib().hvae_svd_spmm(ptr(p), ptr(idx), ptr(vals), n_rows, n_cols, ptr(X), ptr(out), W, stream_of(X)),
+          "hvae_svd_spmm")
+    return out
+
+
+def svd_gram(Y: torch.Tensor, W: int, G: torch.Tensor | None = None) -> torch.Tensor:
+    """G [64, 64] fp64 = Y^T Y, zero outside W x W, exactly symmetric (hvae_svd_gram)."""
+    W = _svd_width("svd_gram", W)
+    _svd_tall("svd_gram", "Y", Y)
+    if G is None:
+        G = torch.empty(SVD_LD, SVD_LD, dtype=torch.float64, device=Y.device)
+    _svd_tall("svd_gram", "G", G, SVD_LD)
+    _svd_alias("svd_gram", Y, G, "Y and G")
+    n = Y.shape[0]
+    ws = workspace(Y.device, lib().hvae_svd_gram_workspace(n))
+    check(lib().hvae_svd_gram(ptr(Y), n, W, ptr(G), ptr(ws), ws.numel(), stream_of(Y)), "hvae_svd_gram")
+    return G
+
+
+def svd_chol_inv(G: torch.Tensor, W: int, flag: torch.Tensor, Rinv: torch.Tensor | None = None) -> torch.Tensor:
+    """Rinv [64, 64] fp64 = R^-1 with G[:W, :W] = R^T R (hvae_svd_chol_inv); flag (int32 [1], device) is set to 1
+    where G is not positive definite to working precision and is never cleared here."""
+    W = _svd_width("svd_chol_inv", W)
+    _svd_tall("svd_chol_inv", "G", G, SVD_LD)
+    require_hip(flag)
+    if flag.dtype != torch.int32 or flag.numel() != 1:
+        raise ValueError(f"svd_chol_inv: flag must be one int32, got {tuple(flag.shape)} {flag.dtype}")
+    if Rinv is None:
+        Rinv = torch.empty_like(G)
+    _svd_tall("svd_chol_inv", "Rinv", Rinv, SVD_LD)
+    _svd_alias("svd_chol_inv", G, Rinv, "G and Rinv")
+    check(lib().hvae_svd_chol_inv(ptr(G), W, ptr(Rinv), ptr(flag), stream_of(G)), "hvae_svd_chol_inv")
+    return Rinv
+
+
+def svd_apply(Y: torch.Tensor, W: int, T: torch.Tensor, W_out: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out[:, :W_out] = Y[:, :W] T[:W, :W_out], zeros from W_out up (hvae_svd_apply); out may be Y (in place), T may
+    alias neither."""
+    W = _svd_width("svd_apply", W)
+    W_out = _svd_width("svd_apply", W_out)
+    _svd_tall("svd_apply", "Y", Y)
+    _svd_tall("svd_apply", "T", T, SVD_LD)
+    if out is None:
+        out = torch.empty_like(Y)
+    _svd_tall("svd_apply", "out", out, Y.shape[0])
+    _svd_alias("svd_apply", T, Y, "T and Y")
+    _svd_alias("svd_apply", T, out, "T and out")
+    check(lib().hvae_svd_apply(ptr(Y), Y.shape[0], W, ptr(T), W_out, ptr(out), stream_of(Y)), "hvae_svd_apply")
+    return out
+
+
+def svd_orthonormalize(Y: torch.Tensor, W: int, flag: torch.Tensor, G: torch.Tensor | None = None,
+                       Rinv: torch.Tensor | None = None) -> torch.Tensor:
+    """CholeskyQR2 in place: Y's W live columns orthonormalised by gram -> chol_inv -> apply, twice. Sound while the
+    condition number of Y^T Y stays far below 2^53 (the sketches of the subspace iteration: at most a few thousand);
+    linearly dependent columns set flag. G, Rinv: two [64, 64] fp64 buffers to reuse."""
+    for _ in range(2):
+        G = svd_gram(Y, W, G)
+        Rinv = svd_chol_inv(G, W, flag, Rinv)
+        svd_apply(Y, W, Rinv, W, out=Y)
+    return Y

@@ -1,0 +1,355 @@
+"""`make baseline-svd` without a GPU: the fixture's own consistency and the float64 restatement of the device
+algorithm against it, the host half of SVDRecommender.fit (the sketch, the eigen step), the command line, both
+Makefile targets, the refused shapes, the results-file merge and the ABI."""
+import argparse
+import json
+import subprocess
+import sys
+from pathlib import Path
+from unittest import mock
+
+import numpy as np
+import pytest
+from scipy.sparse import csr_matrix
+
+import lightgcn_ref as LR
+import svd_ref as SR
+
+ROOT = Path(__file__).resolve().parent.parent
+PKG = ROOT / "recommendation-system_amd"
+ARRAYS = ("components", "user_factors", "singular_values", "evr_sum", "scores")
+
+
+# ----------------------------------------------------------------------------------------------- the fixture ----
+def test_fixture_is_internally_consistent():
+    fx, meta = SR.fixture(), SR.fixture_meta()
+    assert meta["random_state"] == SR.SEED == 42 and meta["bar_factor"] == SR.BAR_FACTOR
+    assert set(meta["bar"]) == {f"{SR.case_key(n, k)}_{a}" for n, k in SR.CASES for a in ARRAYS}
+    for name, k in SR.CASES:
+        matrix, key = SR.case_matrix(name), SR.case_key(name, k)
+        assert SR.matrix_digest(matrix) == meta["data_digest"][name]
+        n_users, n_items = matrix.shape
+        comps, uf, s = fx[f"{key}_components"], fx[f"{key}_user_factors"], fx[f"{key}_singular_values"]
+        assert comps.shape == (k, n_items) and uf.shape == (n_users, k) and s.shape == (k,)
+        assert fx[f"{key}_scores"].shape == (n_users, n_items) and fx[f"{key}_evr_sum"].shape == ()
+        for a in ARRAYS:
+            noise = meta["noise"][f"{key}_{a}"]
+            assert fx[f"{key}_{a}"].dtype == np.float64 and 0 < noise < 1e-11
+            assert meta["bar"][f"{key}_{a}"] == pytest.approx(SR.BAR_FACTOR * noise)
+        # orthonormal components, descending singular values, the sign rule, the factors' products
+        assert np.abs(comps @ comps.T - np.eye(k)).max() < 1e-12 and (np.diff(s) < 0).all()
+        big = np.abs(comps).argmax(axis=1)
+        assert (comps[np.arange(k), big] > 0).all()
+        assert np.abs(matrix @ comps.T - uf).max() < 1e-12 and np.abs(uf @ comps - fx[f"{key}_scores"]).max() < 1e-12
+        assert 0 < fx[f"{key}_evr_sum"] < 1
+        assert meta["exact_svd_miss"][key] > 1e6 * meta["bar"][f"{key}_scores"]
+    assert SR.case_matrix("150x97").shape == (150, 97) and SR.case_matrix("97x150").shape == (97, 150)
+
+
+def test_fixture_ranks_lie_in_their_own_brackets_and_the_brackets_are_tight():
+    fx, meta = SR.fixture(), SR.fixture_meta()
+    name, k = SR.RANKS_CASE
+    matrix, key = SR.case_matrix(name), SR.case_key(name, k)
+    users, tests = LR.fixture_tests(matrix)
+    scores = fx[f"{key}_scores"]
+    tol = 2 * SR.score_bar32(fx[f"{key}_user_factors"], fx[f"{key}_components"], meta["bar"][f"{key}_scores"])
+    assert tol == pytest.approx(meta["rank_tol"])
+    assert fx["ranks"].shape == (len(users),)
+    tight = 0
+    for u, t, rank in zip(users, tests, fx["ranks"]):
+        cand = SR.candidates(matrix, u, t)
+        assert len(cand) < LR.N_NEG  # fewer than 99 negatives exist: nothing is drawn
+        lo, hi = SR.ref_bracket(scores[u], cand, t, 0.0)
+        assert lo <= rank <= hi
+        lo, hi = SR.ref_bracket(scores[u], cand, t, tol)
+        tight += hi - lo <= 1
+    assert tight / len(users) == pytest.approx(meta["tight_bracket_share"]) and tight / len(users) >= 0.9
+
+
+@pytest.mark.parametrize("name,k", SR.CASES)
+def test_restatement_is_within_the_fixture_bars(name, k):
+    """CholeskyQR2 and the Gram eigendecomposition in float64 on the host follow scikit-learn's LU / QR / LAPACK run
+    to within every array's bar; the bars sit ten orders of magnitude below what another rank-k SVD misses by."""
+    fx, meta = SR.fixture(), SR.fixture_meta()
+    key = SR.case_key(name, k)
+    got = SR.fit(SR.case_matrix(name), k)
+    assert got["flag"] == 0 and got["transposed"] == (name == "97x150")
+    got["evr_sum"] = got["explained_variance_ratio"].sum()
+    for a in ARRAYS:
+        err = np.abs(got[a] - fx[f"{key}_{a}"]).max()
+        print(f"{key}_{a}: err {err:.3e} bar {meta['bar'][f'{key}_{a}']:.3e}")
+        assert err <= meta["bar"][f"{key}_{a}"]
+
+
+def test_cholqr2_orthonormalises_the_test_sketches_and_flags_a_rank_deficient_one():
+    for name in ("300x257", "2100x130"):
+        a = LR.kernel_graph(name).astype(np.float64)
+        for W in (18, 60):
+            Y = a @ SR.sketch(a.shape[1], W)
+            Q, flag = SR.cholqr2(Y)
+            assert flag == 0 and np.abs(Q.T @ Q - np.eye(W)).max() <= W * 2.0 ** -53
+            assert np.abs(Q @ (Q.T @ Y) - Y).max() <= 1e-12 * np.abs(Y).max()
+    Y = SR.rank_deficient_rows()
+    assert Y.shape == (120, 60) and np.linalg.matrix_rank(Y) == 40
+    assert SR.cholqr2(Y)[1] == 1 and SR.fit(csr_matrix(Y), 50)["flag"] == 1
+
+
+# --------------------------------------------------------------------------------------- the host half of fit ----
+def test_sketch_is_the_reference_draw_and_leaves_the_global_stream():
+    import src.ml.svd as svd
+    np.random.seed(123)
+    state = LR.state_digest()
+    got = svd.sketch(97, 60)
+    assert LR.state_digest() == state
+    assert np.array_equal(got, np.random.RandomState(42).normal(size=(97, 60))) and got.dtype == np.float64
+    assert np.array_equal(got, SR.sketch(97, 60))
+    assert (svd.RANDOM_STATE, svd.N_OVERSAMPLES, svd.N_ITER) == (42, 10, 5)
+
+
+def test_fit_host_part_leaves_the_global_stream_where_it_was(monkeypatch):
+    """fit with the device calls stubbed by the float64 host restatement of each op: the components come out
+    within the fixture's bar, and numpy's global stream is not touched."""
+    import torch
+    import src.ml.svd as svd
+    ops = svd.ops
+    name, k = "97x150", 8
+    matrix, key = SR.case_matrix(name), SR.case_key(name, k)
+    fx, meta = SR.fixture(), SR.fixture_meta()
+
+    class Image:
+        def __init__(self, m):
+            self.m = m
+
+    def spmm(m, X, W, out=None):
+        r = torch.zeros(m.m.shape[0], ops.SVD_LD, dtype=torch.float64)
+        r[:, :W] = torch.as_tensor(m.m @ X.numpy()[:, :W])
+        return r if out is None else out.copy_(r)
+
+    def orth(Y, W, flag, G=None, Rinv=None):
+        Q, f = SR.cholqr2(Y.numpy()[:, :W].copy())
+        assert f == 0
+        Y[:, :W] = torch.as_tensor(Q)
+        return Y
+
+    def gram(Y, W, G=None):
+        g = torch.zeros(ops.SVD_LD, ops.SVD_LD, dtype=torch.float64)
+        g[:W, :W] = torch.as_tensor(Y.numpy()[:, :W].T @ Y.numpy()[:, :W])
+        return g
+
+    def apply(Y, W, T, W_out, out=None):
+        r = torch.zeros_like(Y)
+        r[:, :W_out] = torch.as_tensor(Y.numpy()[:, :W] @ T.numpy()[:W, :W_out])
+        return r
+
+    a = matrix.astype(np.float64)
+    monkeypatch.setattr(svd, "_resolve_device", lambda d: torch.device("cpu"))
+    monkeypatch.setattr(ops, "csr_from_scipy", lambda m, dev: Image(csr_matrix(a)))
+    monkeypatch.setattr(ops, "csc_from_scipy", lambda m, dev: Image(csr_matrix(a.T)))
+    for fn, stub in (("svd_spmm", spmm), ("svd_orthonormalize", orth), ("svd_gram", gram), ("svd_apply", apply)):
+        monkeypatch.setattr(ops, fn, stub)
+    np.random.seed(7)
+    state = LR.state_digest()
+    model = svd.SVDRecommender(n_components=k)
+    model.fit(matrix)
+    assert LR.state_digest() == state and model.transposed
+    assert model.item_factors.dtype == torch.float64 and model.item_factors.shape == (k, 150)
+    assert model.user_factors.dtype == torch.float64 and model.user_factors.shape == (97, k)
+    for a_name, got in (("components", model.item_factors), ("user_factors", model.user_factors),
+                        ("singular_values", model.singular_values_),
+                        ("evr_sum", model.explained_variance_ratio_.sum())):
+        assert np.abs(got.numpy() - fx[f"{key}_{a_name}"]).max() <= meta["bar"][f"{key}_{a_name}"]
+
+
+def test_eig_transform_orders_descending_and_scales():
+    import src.ml.svd as svd
+    rng = np.random.Generator(np.random.PCG64(3))
+    B = rng.standard_normal((18, 40))
+    G = np.zeros((64, 64))
+    G[:18, :18] = B @ B.T
+    want = np.linalg.svd(B, compute_uv=False)
+    for transposed in (False, True):
+        s, T = svd.eig_transform(G, 18, 8, transposed)
+        assert T.shape == (64, 64) and (T[18:] == 0).all() and (T[:, 8:] == 0).all()
+        np.testing.assert_allclose(s, want[:8], rtol=1e-12)
+        V = T[:18, :8] if transposed else B.T @ T[:18, :8]   # orthonormal either way
+        assert np.abs(V.T @ V - np.eye(8)).max() < 1e-12
+
+
+# ------------------------------------------------------------------------------------------- the command line ----
+def test_cli_flags_and_defaults(monkeypatch):
+    import src.ml.svd as svd
+    seen = {}
+
+    class _Stop(Exception):
+        pass
+
+    def fake_parse(self, args=None, namespace=None):
+        seen["parser"] = self
+        raise _Stop
+
+    monkeypatch.setattr(argparse.ArgumentParser, "parse_args", fake_parse)
+    monkeypatch.setattr(sys, "argv", ["prog"])
+    with pytest.raises(_Stop):
+        svd.main()
+    by_flag = {o: a for a in seen["parser"]._actions for o in a.option_strings}
+    assert set(by_flag) >= {"--data", "--n-negatives", "--k-values", "--n-components"}
+    assert by_flag["--n-negatives"].default == 99 and by_flag["--n-negatives"].type is int
+    assert by_flag["--k-values"].default == [5, 10, 20] and by_flag["--k-values"].nargs == "+"
+    assert by_flag["--n-components"].default == 50 and by_flag["--n-components"].type is int
+
+
+def test_cli_passes_its_arguments():
+    import src.ml.svd as svd
+    argv = ["--data", "d/", "--n-negatives", "0", "--k-values", "3", "7", "--n-components", "12"]
+    with mock.patch.object(svd, "run_svd") as run, mock.patch.object(sys, "argv", ["svd"] + argv):
+        svd.main()
+    args, kw = run.call_args
+    assert args == ("d/", [3, 7], None) and kw == dict(n_components=12)
+
+
+def test_recommender_keeps_the_reference_api_and_defaults():
+    import src.ml.baseline as b
+    import src.ml.svd as svd
+    assert issubclass(svd.SVDRecommender, b.BaseRecommender)
+    m = svd.SVDRecommender()
+    assert m.n_components == 50 and m.user_factors is None and m.item_factors is None
+    assert svd.SVDRecommender(n_components=54).n_components == 54 and svd.SVDRecommender(1).n_components == 1
+    for meth in ("fit", "predict", "score_candidates", "score_all"):
+        assert callable(getattr(m, meth))
+    src = (PKG / "src" / "ml" / "svd.py").read_text()
+    assert "import sklearn" not in src and "from sklearn" not in src
+
+
+@pytest.mark.parametrize("k", [0, 55, -3, 64])
+def test_refused_n_components_names_the_served_range(k):
+    import src.ml.svd as svd
+    with pytest.raises(ValueError) as e:
+        svd.SVDRecommender(n_components=k)
+    assert "1 <= n_components <= 54" in str(e.value) and str(k) in str(e.value)
+
+
+@pytest.mark.parametrize("k", [0, 55])
+def test_cli_refuses_an_unserved_rank_before_reading_data(tmp_path, k):
+    import src.ml.svd as svd
+    with mock.patch.object(sys, "argv", ["svd", "--data", str(tmp_path / "none"), "--n-components", str(k)]):
+        with pytest.raises(ValueError, match="1 <= n_components <= 54"):
+            svd.main()
+
+
+def test_fit_refuses_a_matrix_smaller_than_the_sketch_before_any_device_work(monkeypatch):
+    import src.ml.svd as svd
+    monkeypatch.setattr(svd, "_resolve_device", mock.Mock(side_effect=AssertionError("the device was asked for")))
+    monkeypatch.setattr(svd, "sketch", mock.Mock(side_effect=AssertionError("the sketch was drawn")))
+    m = csr_matrix(np.ones((40, 17)))
+    with pytest.raises(ValueError) as e:
+        svd.SVDRecommender(n_components=8).fit(m)   # 8 + 10 > 17
+    assert "1 <= n_components <= 54" in str(e.value) and "min(n_users, n_items)" in str(e.value)
+    assert "40 x 17" in str(e.value)
+    with pytest.raises(ValueError, match="min"):
+        svd.SVDRecommender(n_components=50).fit(csr_matrix(np.ones((59, 200))))
+
+
+# ------------------------------------------------------------------------------------------- the results file ----
+def test_results_json_merge_keeps_other_entries(tmp_path):
+    import src.ml.svd as svd
+    data = tmp_path / "data"
+    data.mkdir()
+    res = {5: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5}, "training_time_seconds": 1.25}
+    out = svd.merge_results(res, str(data))  # no file yet
+    assert out == tmp_path / "models" / "figures" / "baseline_results.json"
+    assert json.loads(out.read_text()) == {"SVD": {"5": res[5], "training_time_seconds": 1.25}}
+    pop = {"5": {"recall": 0.1, "ndcg": 0.1, "hit_ratio": 0.1}, "training_time_seconds": 0.01}
+    out.write_text(json.dumps({"Popularity": pop, "SVD": {"stale": 1}, "LightGCN": pop}))
+    svd.merge_results(res, str(data))
+    got = json.loads(out.read_text())
+    assert list(got) == ["Popularity", "SVD", "LightGCN"] and got["Popularity"] == pop and got["LightGCN"] == pop
+    assert got["SVD"] == {"5": res[5], "training_time_seconds": 1.25}
+
+
+def test_run_svd_fits_evaluates_and_merges(tmp_path, monkeypatch):
+    """run_svd with the device work stubbed out: the train + val matrix, the test frame, the timing entry."""
+    import src.ml.svd as svd
+    from gen import write_planted_artifacts
+    data, _ = write_planted_artifacts(tmp_path, dict(n_users=30, n_items=40, d=4, n_clusters=2))
+    calls = []
+
+    def fake_fit(self, m):
+        self.device = None
+        calls.append(("fit", m.shape, self.n_components))
+
+    def fake_eval(model, name, matrix, test_df, u2i, i2i, k_values, n_negatives):
+        calls.append((name, matrix.shape, len(test_df), tuple(k_values), n_negatives))
+        return {k: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5} for k in k_values}
+
+    monkeypatch.setattr(svd.SVDRecommender, "fit", fake_fit)
+    monkeypatch.setattr(svd, "evaluate_model", fake_eval)
+    monkeypatch.setattr(svd.torch.cuda, "synchronize", lambda *a, **k: None)
+    res = svd.run_svd(str(data), [5, 10], None, n_components=8)
+    assert calls == [("fit", (30, 40), 8), ("SVD", (30, 40), 30, (5, 10), None)]
+    out = json.loads((tmp_path / "models" / "figures" / "baseline_results.json").read_text())
+    assert list(out) == ["SVD"] and list(out["SVD"]) == ["5", "10", "training_time_seconds"]
+    assert isinstance(out["SVD"]["training_time_seconds"], float) and set(res) == {5, 10, "training_time_seconds"}
+
+
+@pytest.mark.parametrize("target,n_neg", [("baseline-svd", "99"), ("baseline-svd-full", "0")])
+def test_makefile_targets(target, n_neg):
+    r = subprocess.run(["make", "-n", "-C", str(PKG), target, "PYTHON=python", "DATA_DIR=data"], capture_output=True,
+                       text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert f"python -m src.ml.svd --data data/ --n-negatives {n_neg}" in r.stdout.splitlines()
+    mk = (PKG / "Makefile").read_text()
+    phony = mk[mk.index(".PHONY"):mk.index("\nlib:")]
+    assert f" {target}" in phony and "make baseline-svd " in mk
+
+
+def test_baseline_module_still_refuses_svd_and_points_here(tmp_path):
+    import src.ml.baseline as b
+    assert b.SERVED_MODELS == ("Popularity", "Item-KNN")
+    with mock.patch.object(sys, "argv", ["baseline", "--data", str(tmp_path / "none"), "--models", "SVD"]):
+        with pytest.raises(ValueError) as e:
+            b.main()
+    assert "Popularity" in str(e.value) and "Item-KNN" in str(e.value) and "src.ml.svd" in str(e.value)
+    assert "src.ml.lightgcn" in str(e.value)
+
+
+# ------------------------------------------------------------------------------------------------------ the ABI ----
+def test_abi_declares_binds_and_wraps_the_entry_points():
+    from hvae import _lib, ops
+    header = (ROOT / "include" / "hvae.h").read_text()
+    for name in ("hvae_svd_spmm", "hvae_svd_gram", "hvae_svd_gram_workspace", "hvae_svd_chol_inv", "hvae_svd_apply"):
+        assert f"{name}(" in header and name in _lib.SIGNATURES
+    assert "#define HVAE_ABI_VERSION 6" in header and _lib.ABI_VERSION == 6
+    assert f"#define HVAE_SVD_LD {_lib.SVD_LD}" in header and _lib.SVD_LD == ops.SVD_LD == 64 and "(K19)" in header
+    for fn in ("svd_spmm", "svd_gram", "svd_chol_inv", "svd_apply", "svd_orthonormalize"):
+        assert callable(getattr(ops, fn))
+    assert len(_lib.SIGNATURES["hvae_svd_spmm"][1]) == 9 and len(_lib.SIGNATURES["hvae_svd_gram"][1]) == 7
+    assert len(_lib.SIGNATURES["hvae_svd_chol_inv"][1]) == 5 and len(_lib.SIGNATURES["hvae_svd_apply"][1]) == 7
+
+
+def test_wrappers_refuse_bad_arguments_before_any_launch(monkeypatch):
+    """Width outside 1..64, a wrong dtype or leading dimension, and aliasing: a ValueError that names the served
+    range, raised from the argument checks alone (the tensors are host tensors behind a stubbed device check)."""
+    import torch
+    from hvae import ops
+    monkeypatch.setattr(ops, "require_hip", lambda *a: None)
+    monkeypatch.setattr(ops, "lib", mock.Mock(side_effect=AssertionError("a kernel was launched")))
+    Y = torch.zeros(10, 64, dtype=torch.float64)
+    G, T = torch.zeros(64, 64, dtype=torch.float64), torch.zeros(64, 64, dtype=torch.float64)
+    flag = torch.zeros(1, dtype=torch.int32)
+    for W in (0, 65, -1):
+        for call in (lambda: ops.svd_gram(Y, W), lambda: ops.svd_chol_inv(G, W, flag),
+                     lambda: ops.svd_apply(Y, W, T, 8), lambda: ops.svd_apply(Y, 8, T, W)):
+            with pytest.raises(ValueError, match="1 to 64"):
+                call()
+    with pytest.raises(ValueError, match="float64"):
+        ops.svd_gram(Y.float(), 8)
+    with pytest.raises(ValueError, match="leading dimension 64"):
+        ops.svd_gram(torch.zeros(10, 32, dtype=torch.float64), 8)
+    with pytest.raises(ValueError, match="leading dimension 64"):
+        ops.svd_apply(torch.zeros(10, 128, dtype=torch.float64)[:, :64], 8, T, 8)
+    with pytest.raises(ValueError, match="alias"):
+        ops.svd_chol_inv(G, 8, flag, Rinv=G)
+    with pytest.raises(ValueError, match="alias"):
+        ops.svd_apply(G, 8, G, 8)
+    with pytest.raises(ValueError, match="int32"):
+        ops.svd_chol_inv(G, 8, flag.long())
