@@ -45,7 +45,8 @@ int hvae_version(void);
 int hvae_last_error(char* buf, size_t len);
 /* Live kernel timing for benchmarks: arm one kernel by name ("decoder_sweep",
  * "decoder_finalize", "adam_rows", "adam_dense", "encoder_fwd", "gemm",
- * "ln_bwd", "rowgrad_apply", "clip"); its next max_launches launches
+ * "ln_bwd", "rowgrad_apply", "clip", "mvae_encoder_fwd", "mvae_tanh_drop_fwd",
+ * "mvae_tanh_drop_bwd", "mvae_nll"); its next max_launches launches
  * (outside stream capture) are bracketed by a hipEvent pair recorded on the
  * launch stream. hvae_probe_collect synchronizes those events and returns the
  * mean launch duration. hvae_probe_arm(NULL, 0) disarms. */
@@ -804,6 +805,53 @@ int hvae_svd_chol_inv(const double* G, int64_t W, double* Rinv, int32_t* flag, v
  * of Y's columns, is gram -> chol_inv -> apply(Y, Rinv) in place, twice. */
 int hvae_svd_apply(const double* Y, int64_t n, int64_t W, const double* T, int64_t W_out, double* out,
                    void* stream);
+
+/* -------------------------------------------------------- Mult-VAE (K20) -- */
+/* The Mult-VAE baseline (MultVAE / MultVAERecommender, src/ml/baseline.py:126-231): the three pieces the library had
+ * no kernel for. Every dense product of that model is hvae_gemm_f32 (bias through HVAE_EPI_BIAS), its bias gradients
+ * hvae_colsum, the first layer's weight gradient hvae_w1_rowgrad, its latent hvae_reparam_kl_*, its optimiser
+ * hvae_adam_rows / hvae_adam_dense. All fp32 without floating-point atomics or approximate tanh / exp / log; every
+ * sum has one fixed order (csrc/hvae_mvae.hip states each), so two runs are bitwise equal.
+ *
+ * Dropout multipliers are 0 or 1 / (1 - p). With train = 0 there is no dropout anywhere and seed / step are not
+ * read. With train != 0 they are the injected arrays where given (parity mode), else Philox(seed, *step_dev, tag,
+ * element): tag 0x400 is the input mask with element b * N + j (b the batch row, j the item: independent of the CSR
+ * layout), 0x401 and 0x402 the two hidden masks with element b * H + h.
+ *
+ * hvae_mvae_encoder_fwd: Dropout -> F.normalize(p=2, dim=1) -> Linear(N, H) -> Tanh -> Dropout over sparse rows.
+ * Per batch row b with stored entries e (items j_e, values x_e, 2.0 and more occur):
+ *   den = max(||x_b||_2, 1e-12f);  xs_e = (x_e / den) * in_mult_e
+ *   a_b = b1 + sum_e xs_e * w1t[j_e]    (entries in storage order, one fma chain per column)
+ *   t = tanh(a);  h = t * mult          (an empty row gives h = Drop(tanh(b1)))
+ * w1t is the item-major [N, H] image of encoder.0.weight. in_mult (nullable) and xs_out (nullable) are indexed
+ * exactly like x->vals, so a second hvae_csr_batch with vals = xs_out feeds hvae_w1_rowgrad; drop_mult (nullable)
+ * is [nb, H]; t_out (nullable) and h_out are [nb, H]. H: a multiple of 4 in 4 .. 2048, else HVAE_ERR_UNSUPPORTED.
+ * An item id outside [0, n_items) gives NaN in its row, never a read out of bounds. */
+int hvae_mvae_encoder_fwd(const hvae_csr_batch* x, const float* w1t, const float* b1, int64_t H, float p_in,
+                          float p_drop, const float* in_mult, const float* drop_mult, uint64_t seed,
+                          const int64_t* step_dev, int train, float* xs_out, float* t_out, float* h_out,
+                          void* stream);
+/* Elementwise over [nb, W] with leading dimensions (multiples of 4; W a multiple of 4; pointers 16-B aligned):
+ *   fwd: t = tanh(a), h = t * mult        bwd: da = dh * mult * (1 - t^2)
+ * mult is drop_mult [nb, W] (contiguous) where given, else Philox(tag) with element b * W + w; p_drop = 0 without
+ * drop_mult, or train = 0, means no mask, and h_out may then be t_out. t_out (nullable) may be a; da may be dh. */
+int hvae_mvae_tanh_drop_fwd(const float* a, int64_t lda, int64_t nb, int64_t W, float p_drop,
+                            const float* drop_mult, uint64_t seed, const int64_t* step_dev, uint32_t tag, int train,
+                            float* t_out, float* h_out, int64_t ldo, void* stream);
+int hvae_mvae_tanh_drop_bwd(const float* dh, int64_t ldd, const float* t, int64_t ldt, int64_t nb, int64_t W,
+                            float p_drop, const float* drop_mult, uint64_t seed, const int64_t* step_dev,
+                            uint32_t tag, int train, float* da, int64_t lda, void* stream);
+/* The multinomial loss and its gradient against the sparse target x, in place over stored logits S [nb, lds]
+ * (N = x->n_items <= lds; row b of S belongs to batch row b of x). Per row:
+ *   lse[b] = logsumexp_j S[b, j] (max-subtracted);  recon_rows[b] = -sum_e x_e (S[b, j_e] - lse[b]);  n_b = sum_e x_e
+ *   S[b, j] <- grad_scale * (n_b * exp(S[b, j] - lse[b]) - x_bj)     for j < N
+ * X is never densified. One block per row: the entry logits are read, a barrier, the dense pass, a barrier, then
+ * the sparse subtraction (rounded last). PRECONDITION: no duplicate column within a row (two threads would race on
+ * it); _build_input_matrix's scipy CSR sums duplicates. Columns N .. lds - 1 are neither read nor written. A row
+ * with n_b = 0 gets a zero gradient, recon 0 and a valid lse. An item id outside [0, N) makes its row's recon NaN,
+ * never an access out of bounds. */
+int hvae_mvae_nll(const hvae_csr_batch* x, float* S, int64_t lds, float grad_scale, float* lse, float* recon_rows,
+                  void* stream);
 
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and

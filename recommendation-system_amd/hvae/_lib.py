@@ -27,6 +27,10 @@ EPI_NONE, EPI_BIAS, EPI_BIAS_GELU_DROP, EPI_GELU_DROP_BWD, EPI_DROP_BWD, EPI_REP
 TAG_ENC_DROP = 0x100
 TAG_PROJ_DROP = 0x200
 TAG_EPS = 0x300
+# csrc/hvae_mvae.hip: the Mult-VAE input mask and its two hidden masks
+TAG_MVAE_IN = 0x400
+TAG_MVAE_HID1 = 0x401
+TAG_MVAE_HID2 = 0x402
 
 ROWSQ_PARTS = 16  # include/hvae.h HVAE_ROWSQ_PARTS
 
@@ -233,6 +237,10 @@ SIGNATURES = {
     "hvae_svd_gram": (cint, [vp, i64, i64, vp, vp, sz, vp]),
     "hvae_svd_chol_inv": (cint, [vp, i64, vp, vp, vp]),
     "hvae_svd_apply": (cint, [vp, i64, i64, vp, i64, vp, vp]),
+    "hvae_mvae_encoder_fwd": (cint, [P(CsrBatch), vp, vp, i64, f32, f32, vp, vp, u64, vp, cint, vp, vp, vp, vp]),
+    "hvae_mvae_tanh_drop_fwd": (cint, [vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, vp, i64, vp]),
+    "hvae_mvae_tanh_drop_bwd": (cint, [vp, i64, vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, i64, vp]),
+    "hvae_mvae_nll": (cint, [P(CsrBatch), vp, i64, f32, vp, vp, vp]),
     "hvae_cast_bf16": (cint, [vp, vp, i64, vp]),
     "hvae_negatives_legacy": (cint, [vp, vp, vp, i64, vp, i64, vp, vp, i64, C.c_int32, vp, vp]),
     "hvae_read_interactions": (cint, [C.c_char_p, C.c_char_p, i64, i64, C.c_char_p, i64, i64, cint,

@@ -878,3 +878,123 @@ def svd_orthonormalize(Y: torch.Tensor, W: int, flag: torch.Tensor, G: torch.Ten
         Rinv = svd_chol_inv(G, W, flag, Rinv)
         svd_apply(Y, W, Rinv, W, out=Y)
     return Y
+
+
+# ----------------------------------------------------------------- Mult-VAE --
+MVAE_MAX_HIDDEN = 2048  # hvae_mvae_encoder_fwd (include/hvae.h)
+MVAE_MAX_LATENT = 1024
+
+
+def _mvae_width(what: str, name: str, W: int, hi: int) -> int:
+    if not (4 <= int(W) <= hi and int(W) % 4 == 0):
+        raise ValueError(f"{what}: {name} = {W} is not served; served: multiples of 4 from 4 to {hi}")
+    return int(W)
+
+
+def _mvae_mat(what: str, name: str, t: torch.Tensor | None, nb: int, W: int, contiguous: bool = False):
+    if t is None:
+        return
+    require_hip(t)
+    if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (nb, W) or t.stride(1) != 1 \
+            or t.stride(0) % 4 or t.stride(0) < W or t.data_ptr() % 16 or (contiguous and t.stride(0) != W):
+        raise ValueError(f"{what}: {name} must be a float32 [{nb}, {W}] matrix with unit column stride, a leading "
+                         f"dimension that is a multiple of 4{' and equal to its width' if contiguous else ''} and a "
+                         f"16-byte aligned base, got {tuple(t.shape)} {t.dtype} with strides {tuple(t.stride())}")
+
+
+def mvae_encoder_fwd(x: Csr, w1t: torch.Tensor, b1: torch.Tensor, p_in: float, p_drop: float, train: bool,
+                     seed: int = 0, step=None, in_mult=None, drop_mult=None, xs_out=None, t_out=None, h_out=None,
+                     save: bool = True):
+    """The Mult-VAE first layer over sparse rows (hvae_mvae_encoder_fwd) -> (h [nb, H], t [nb, H] or None, xs or
+    None). xs and in_mult are indexed like x.vals; drop_mult is [nb, H]."""
+    what = "mvae_encoder_fwd"
+    require_hip(w1t, b1, in_mult, drop_mult, xs_out, t_out, h_out)
+    if w1t.dim() != 2 or not w1t.is_contiguous() or w1t.shape[0] != x.n_items or w1t.dtype != torch.float32:
+        raise ValueError(f"{what}: w1t must be a contiguous float32 [n_items = {x.n_items}, H] matrix, got "
+                         f"{tuple(w1t.shape)}")
+    H = _mvae_width(what, "H", w1t.shape[1], MVAE_MAX_HIDDEN)
+    if tuple(b1.shape) != (H,) or not b1.is_contiguous():
+        raise ValueError(f"{what}: b1 must be a contiguous [{H}] vector, got {tuple(b1.shape)}")
+    if in_mult is not None and (in_mult.numel() != x.vals.numel() or in_mult.dtype != torch.float32):
+        raise ValueError(f"{what}: in_mult must be float32 and indexed like x.vals ({x.vals.numel()} entries)")
+    dev = w1t.device
+    if h_out is None:
+        h_out = torch.empty(x.nb, H, device=dev)
+    if t_out is None and save:
+        t_out = torch.empty(x.nb, H, device=dev)
+    if xs_out is None and save:
+        xs_out = torch.empty_like(x.vals)
+    if xs_out is not None and (xs_out.numel() != x.vals.numel() or xs_out.dtype != torch.float32):
+        raise ValueError(f"{what}: xs_out must be float32 and indexed like x.vals ({x.vals.numel()} entries)")
+    for name, t in (("drop_mult", drop_mult), ("t_out", t_out), ("h_out", h_out)):
+        _mvae_mat(what, name, t, x.nb, H, contiguous=True)
+    check(lib().hvae_mvae_encoder_fwd(x.ref, ptr(w1t), ptr(b1), H, float(p_in), float(p_drop), ptr(in_mult),
+                                      ptr(drop_mult), int(seed), ptr(step), int(train), ptr(xs_out), ptr(t_out),
+                                      ptr(h_out), stream_of(w1t)), "hvae_mvae_encoder_fwd")
+    return h_out, t_out, xs_out
+
+
+def mvae_tanh_drop_fwd(a: torch.Tensor, p_drop: float, train: bool, tag: int, seed: int = 0, step=None,
+                       drop_mult=None, t_out=None, h_out=None):
+    """t = tanh(a), h = t * mult over [nb, W] views (hvae_mvae_tanh_drop_fwd) -> (h, t). t_out may be a; without a
+    mask h_out may be t_out (the default then: one tensor)."""
+    what = "mvae_tanh_drop_fwd"
+    nb, W = a.shape
+    _mvae_width(what, "W", W, 1 << 24)
+    masked = bool(train) and (drop_mult is not None or p_drop > 0)
+    if t_out is None:
+        t_out = torch.empty(nb, W, device=a.device)
+    if h_out is None:
+        h_out = torch.empty(nb, W, device=a.device) if masked else t_out
+    if t_out.stride(0) != h_out.stride(0):
+        raise ValueError(f"{what}: t_out and h_out must share a leading dimension")
+    _mvae_mat(what, "a", a, nb, W)
+    _mvae_mat(what, "t_out", t_out, nb, W)
+    _mvae_mat(what, "h_out", h_out, nb, W)
+    _mvae_mat(what, "drop_mult", drop_mult, nb, W, contiguous=True)
+    if masked and h_out.data_ptr() in (t_out.data_ptr(), a.data_ptr()):
+        raise ValueError(f"{what}: h_out may alias t_out or a only without a mask")
+    check(lib().hvae_mvae_tanh_drop_fwd(ptr(a), a.stride(0), nb, W, float(p_drop), ptr(drop_mult), int(seed),
+                                        ptr(step), int(tag), int(train), ptr(t_out), ptr(h_out), h_out.stride(0),
+                                        stream_of(a)), "hvae_mvae_tanh_drop_fwd")
+    return h_out, t_out
+
+
+def mvae_tanh_drop_bwd(dh: torch.Tensor, t: torch.Tensor, p_drop: float, train: bool, tag: int, seed: int = 0,
+                       step=None, drop_mult=None, da=None):
+    """da = dh * mult * (1 - t^2) (hvae_mvae_tanh_drop_bwd); da may be dh."""
+    what = "mvae_tanh_drop_bwd"
+    nb, W = t.shape
+    _mvae_width(what, "W", W, 1 << 24)
+    if da is None:
+        da = torch.empty(nb, W, device=t.device)
+    _mvae_mat(what, "dh", dh, nb, W)
+    _mvae_mat(what, "t", t, nb, W)
+    _mvae_mat(what, "da", da, nb, W)
+    _mvae_mat(what, "drop_mult", drop_mult, nb, W, contiguous=True)
+    if da.data_ptr() == t.data_ptr():
+        raise ValueError(f"{what}: da may alias dh, not t")
+    check(lib().hvae_mvae_tanh_drop_bwd(ptr(dh), dh.stride(0), ptr(t), t.stride(0), nb, W, float(p_drop),
+                                        ptr(drop_mult), int(seed), ptr(step), int(tag), int(train), ptr(da),
+                                        da.stride(0), stream_of(t)), "hvae_mvae_tanh_drop_bwd")
+    return da
+
+
+def mvae_nll(x: Csr, S: torch.Tensor, grad_scale: float, lse=None, recon_rows=None):
+    """The multinomial loss against the sparse rows x and its gradient, in place over the stored logits S [nb, >= N]
+    (hvae_mvae_nll) -> (lse [nb], recon_rows [nb]); S[:, :N] becomes grad_scale * (n softmax(S) - x). No column may
+    occur twice in a row of x."""
+    require_hip(S, lse, recon_rows)
+    if S.dtype != torch.float32 or S.dim() != 2 or S.shape[0] != x.nb or S.stride(1) != 1 or S.shape[1] < x.n_items \
+            or S.stride(0) < S.shape[1]:
+        raise ValueError(f"mvae_nll: S must be a float32 [nb = {x.nb}, >= {x.n_items}] matrix with unit column "
+                         f"stride, got {tuple(S.shape)} {S.dtype} with strides {tuple(S.stride())}")
+    if lse is None:
+        lse = torch.empty(x.nb, device=S.device)
+    if recon_rows is None:
+        recon_rows = torch.empty(x.nb, device=S.device)
+    if lse.numel() != x.nb or recon_rows.numel() != x.nb:
+        raise ValueError(f"mvae_nll: lse and recon_rows must hold nb = {x.nb} floats")
+    check(lib().hvae_mvae_nll(x.ref, ptr(S), S.stride(0), float(grad_scale), ptr(lse), ptr(recon_rows),
+                              stream_of(S)), "hvae_mvae_nll")
+    return lse, recon_rows

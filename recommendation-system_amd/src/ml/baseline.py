@@ -4,8 +4,8 @@ Served: the two training-free baselines, Popularity and Item-KNN (reference: bas
 reference's recommender API (fit / predict), evaluate_model (:411-471), run_all_baselines (:474-533) and CLI
 (:536-544), and the same models/figures/baseline_results.json. SVD, Mult-VAE and LightGCN are separate trained
 models and are not run from here: asking for one is an error, never a silent skip. LightGCN is trained by
-src/ml/lightgcn.py (`make baseline-lightgcn`) and SVD fitted by src/ml/svd.py (`make baseline-svd`); both reuse this
-module's evaluation and results file.
+src/ml/lightgcn.py (`make baseline-lightgcn`), SVD fitted by src/ml/svd.py (`make baseline-svd`) and Mult-VAE trained
+by src/ml/multvae.py (`make baseline-multvae`); all three reuse this module's evaluation and results file.
 
 The reference scores one test row at a time in a Python loop; here the rows are batched on the device. Scores
 come from libhvae (hvae_csc_col_stats for Popularity, the two-stage hvae_knn_* kernels for Item-KNN), the
@@ -275,7 +275,7 @@ def _select_models(models) -> list[str]:
         raise ValueError(f"baseline model(s) {bad} are not served on this path: only {SERVED_MODELS[0]} and "
                          f"{SERVED_MODELS[1]} are ({', '.join(REFERENCE_ONLY_MODELS)} are separate trained models "
                          "that are not run from here; LightGCN has its own command, python -m src.ml.lightgcn, "
-                         "SVD has python -m src.ml.svd, Mult-VAE exists in the reference only)")
+                         "SVD has python -m src.ml.svd, Mult-VAE has python -m src.ml.multvae)")
     return names
 
 
