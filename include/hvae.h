@@ -580,6 +580,26 @@ int hvae_adam_lazy_catchup_csr_pending(const hvae_adam* cfg, const float* tab, f
                                        const hvae_adam_pend* pend, void* stream);
 int hvae_adam_lazy_pending(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v, int32_t* last_step,
                            int64_t N, int64_t H, int64_t max_rows, const hvae_adam_pend* pend, void* stream);
+/* hvae_adam_lazy_pending as a guest beside the decoder sweep: the same arguments, rows, preconditions and results
+ * (p, m, v and last_step bitwise), from a kernel of one-wave blocks within 32 VGPRs, no LDS and no scratch, which
+ * fits on a SIMD beside the d = 768 sweep's two waves. max_rows sizes the grid as in hvae_adam_lazy_pending; rows
+ * recorded beyond it are still taken. To be launched on a stream of its own, forked after the last forward launch
+ * and before hvae_decoder_train.
+ * hvae_adam_guest_hold: one wave that sleeps `us` microseconds (0 .. 1000; a bounded loop on the constant clock),
+ *   to be launched in front of the guest on its stream so that the sweep's blocks become resident first.
+ * hvae_adam_pending_guest_fits: whether, by the loaded code objects' registers and LDS, a guest wave fits beside
+ *   the sweep hvae_decoder_train would launch for (dtype, B, N, D) -- 1 / 0; 0 too for a sweep whose footprint the
+ *   query does not read (it reads the d = 768 bf16 sweep's).
+ * hvae_adam_guest_fit_calc: that arithmetic alone (pure, no device): how many guest waves fit on one SIMD beside
+ *   sweep_waves_per_simd waves of sweep_regs registers -- allocation granule 8 out of 512, 160 KiB of LDS and 32
+ *   waves a CU. */
+int hvae_adam_lazy_pending_guest(const hvae_adam* cfg, const float* tab, float* p, float* m, float* v,
+                                 int32_t* last_step, int64_t N, int64_t H, int64_t max_rows,
+                                 const hvae_adam_pend* pend, void* stream);
+int hvae_adam_guest_hold(int64_t us, void* stream);
+int hvae_adam_pending_guest_fits(int dtype, int64_t B, int64_t N, int64_t D);
+int hvae_adam_guest_fit_calc(int sweep_waves_per_simd, int sweep_regs, int64_t sweep_lds_bytes, int guest_regs,
+                             int64_t guest_lds_bytes);
 /* *counter += delta (device-side step/batch counters for graph replay). */
 int hvae_counter_add(int64_t* counter, int64_t delta, void* stream);
 /* *a += da and, if b != NULL, *b += db, in one launch (end of a train step). */

@@ -144,6 +144,16 @@ struct ProbeScope {
   ~ProbeScope() { probe_mark(name, st, false); }
 };
 
+// What the decoder sweep that hvae_decoder_train would launch for a shape occupies on a CU, read from its loaded
+// code object (hvae_decoder.hip; hvae_adam_pending_guest_fits). False where the plan's sweep is not one whose
+// kernel and launch size this query knows: the d = 768 bf16 sweep (k_dec5_bf16) is the one it reads.
+struct SweepFootprint {
+  int waves_per_simd;  // of one block, the most a CU holds beside a guest
+  int regs;            // VGPRs + AGPRs per lane as the code object requests them
+  size_t lds_bytes;    // static + dynamic
+};
+bool dec_sweep_footprint(int dtype, int64_t nb, int64_t N, int64_t D, SweepFootprint* out);
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // --------------------------------------------------------------- device ----

@@ -1918,6 +1918,33 @@ extern "C" size_t hvae_decoder_workspace(int dtype, int64_t nb, int64_t N, int64
   return plan_ws_bytes(dec_plan(dtype, nb, N, D, SIZE_MAX, dec_ab()), nb, D);
 }
 
+// k_dec5_bf16 is defined in hvae_decoder5.hip; declared here only to ask the runtime for its attributes. The
+// declaration must match that definition (template parameter, launch bounds, argument list): if the two drift, the
+// library fails to link or load, nothing subtler.
+namespace hvae {
+namespace dec5 {
+template <bool WITH_O>
+__global__ void __launch_bounds__(512) k_dec5_bf16(const float* __restrict__ U, int64_t ldu,
+                                                   const bf16_t* __restrict__ E, const float* __restrict__ e_maxnorm,
+                                                   int64_t nb, int64_t N, int splits, int64_t tiles_per_split,
+                                                   Out out);
+}  // namespace dec5
+
+bool dec_sweep_footprint(int dtype, int64_t nb, int64_t N, int64_t D, SweepFootprint* out) {
+  if (!out || nb <= 0 || N <= 0 || D <= 0) return false;
+  const DecPlan p = dec_plan(dtype, nb, N, D, SIZE_MAX, dec_ab());
+  if (p.sweep != DecSweep::bf16_v5) return false;
+  hipFuncAttributes fa{};
+  if (hipFuncGetAttributes(&fa, (const void*)dec5::k_dec5_bf16<true>) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  // a 512-thread block is 8 waves, two a SIMD; its LDS leaves no room for a second block on the CU
+  *out = SweepFootprint{512 / kWave / 4, fa.numRegs, fa.sharedSizeBytes + (size_t)dec5::LDS_BYTES};
+  return true;
+}
+}  // namespace hvae
+
 // the finalize's 16-B column form: every row operand it reads or writes starts 16-B aligned
 static bool fin_v4(const FinArgs& a) {
   auto al = [](const void* p) { return ((uintptr_t)p % 16) == 0; };

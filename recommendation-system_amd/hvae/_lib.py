@@ -214,6 +214,10 @@ SIGNATURES = {
                                     vp]),
     "hvae_adam_lazy_catchup_csr_pending": (cint, [P(Adam), vp, vp, vp, vp, vp, P(CsrBatch), i64, P(AdamPend), vp]),
     "hvae_adam_lazy_pending": (cint, [P(Adam), vp, vp, vp, vp, vp, i64, i64, i64, P(AdamPend), vp]),
+    "hvae_adam_lazy_pending_guest": (cint, [P(Adam), vp, vp, vp, vp, vp, i64, i64, i64, P(AdamPend), vp]),
+    "hvae_adam_guest_hold": (cint, [i64, vp]),
+    "hvae_adam_pending_guest_fits": (cint, [cint, i64, i64, i64]),
+    "hvae_adam_guest_fit_calc": (cint, [cint, cint, i64, cint, i64]),
     "hvae_counter_add": (cint, [vp, i64, vp]),
     "hvae_counters_add": (cint, [vp, i64, vp, i64, vp]),
     "hvae_score_candidates": (cint, [vp, i64, vp, vp, i64, vp, i64, i64, vp, vp]),

@@ -34,6 +34,18 @@ from . import _lib, ops
 from ._lib import CsrBatch, Epilogue, GemmDesc, check, lib, ptr
 
 ALIGN = 4  # floats: every flat segment starts 16-B aligned
+# A single-GPU deferring step runs its recorded W1t update as a guest under the decoder sweep by default where it
+# fits (FusedTrainer._use_guest: the d = 768 bf16 sweep); HVAE_DEFER_AT=guest asks for it either way, data-parallel
+# steps included (not measured: they keep "sweep" by default), any other value turns it off. Syn-10M bf16: 10.344 -> 10.131 and, on another device, 10.029 -> 9.891 ms per step, every run of
+# three faster, 8.7 x the parent's own range both times (DESIGN.md 4.2 "The recorded update as a guest of the
+# sweep", profiles/adam_guest_ab.jsonl).
+GUEST_DEFAULT = True
+# The hold in front of the guest on its stream (hvae_adam_guest_hold), microseconds. The hold starts when the last
+# forward kernel ends (the fork event). In the step's kernel trace the sweep starts 12 us after that kernel's end
+# with the fork in the graph (0 us without it) and 6 us after the hold does (medians over 29 steps,
+# profiles/adam_guest_ab.jsonl); its 256 blocks are dispatched within a few microseconds more, which a kernel trace
+# does not show. The hold is that plus a margin, after which the guest's first block starts 15.5 us behind the sweep's.
+GUEST_HOLD_US = 20
 
 
 def _align(n: int) -> int:
@@ -383,7 +395,21 @@ class FusedTrainer:
         self.adam_defer = self.lazy_adam and (bool(int(env_defer)) if env_defer is not None
                                               else lay.n_items >= (1 << 19))
         self.defer_at = os.environ.get("HVAE_DEFER_AT", "sweep")
+        # HVAE_DEFER_AT=guest: under the decoder sweep, as a guest kernel written to fit beside its waves
+        # (hvae_adam_lazy_pending_guest), forked after the last forward launch; only where the loaded code objects
+        # say it fits beside the sweep of that batch size (hvae_adam_pending_guest_fits), else "sweep". With
+        # HVAE_DEFER_AT unset it is the default where it fits and was measured: single-GPU steps (GUEST_DEFAULT;
+        # data-parallel steps take it only when asked); everywhere else the step is unchanged launch for launch.
+        self._guest_asked = self.defer_at == "guest"
+        self._guest_on = self.adam_defer and (self._guest_asked or
+                                              (GUEST_DEFAULT and "HVAE_DEFER_AT" not in os.environ))
+        if self.defer_at == "guest":
+            self.defer_at = "sweep"  # where the guest does not fit
+        self._guest_fits: dict[int, bool] = {}
         self._pend_open = False  # (host-tracked) a recorded update may still be pending on the device
+        if self._guest_on:
+            # the guest's stream has the lowest priority torch offers (the numerically largest of its range)
+            self.guest_stream = torch.cuda.Stream(device, priority=max(torch.cuda.Stream.priority_range()))
         if self.adam_defer:
             self.pend_slot = torch.zeros(lay.n_items, dtype=torch.int32, device=device)
             self.pend_item = torch.zeros(lay.n_items, dtype=torch.int32, device=device)
@@ -635,6 +661,11 @@ class FusedTrainer:
         s = _Step(self, bf, csr, train, beta, p_drop, ext)
         ev_plan, ev_defer = self._step_prologue(s)
         self._step_forward(s)
+        if train and s.sched.defer and ev_defer is None and self._use_guest(bf.B):
+            # HVAE_DEFER_AT=guest: forked after the last forward launch, under the decoder sweep. The hazards are
+            # those of "fwd", which forks even earlier: the batch's rows were claimed by the catch-up before the
+            # fork, and the encoder (done by now) reads only those rows; the sweep reads no W1t row at all.
+            ev_defer = self._launch_pending(s, guest=True)
         self._step_decoder(s)
         if not train:
             return
@@ -643,13 +674,29 @@ class FusedTrainer:
         self._step_backward(s)
         self._step_finish(s, ev_plan, ev_defer)
 
-    def _launch_pending(self, s: "_Step") -> torch.cuda.Event:
+    def _launch_pending(self, s: "_Step", guest: bool = False) -> torch.cuda.Event:
         """The last step's recorded W1t update, for the rows this batch's catch-up did not take, on the defer
-        stream from here on. Returns the event the row-gradient apply waits for."""
-        ds = self.defer_stream
+        stream (guest: on the guest's stream, by the guest kernel) from here on. Returns the event the row-gradient
+        apply waits for."""
+        ds = self.guest_stream if guest else self.defer_stream
         self._fork(s.main, ds)
-        self._apply_pending(min(self.layout.n_items, s.bf.cap), ds.cuda_stream)
+        if guest:  # the sweep's blocks resident first
+            check(lib().hvae_adam_guest_hold(GUEST_HOLD_US, ds.cuda_stream), "adam_guest_hold")
+        # (the cap of this step's buffers is a grid-size hint: the record is the previous step's, whose batch may
+        # have been larger -- a full batch before the epoch's tail -- and both kernels walk all of its rows)
+        self._apply_pending(min(self.layout.n_items, s.bf.cap), ds.cuda_stream, guest)
         return self._record(ds)
+
+    def _use_guest(self, B: int) -> bool:
+        """Whether a deferring train step of B users runs its recorded update under the decoder sweep
+        (HVAE_DEFER_AT=guest, or by default where GUEST_DEFAULT): only where the guest fits beside that sweep, and
+        by default only on a single GPU, where it was measured."""
+        if not self._guest_on or (self.dp is not None and not self._guest_asked):
+            return False
+        if B not in self._guest_fits:
+            lay = self.layout
+            self._guest_fits[B] = bool(lib().hvae_adam_pending_guest_fits(self.dec_dtype, B, lay.n_items, lay.d))
+        return self._guest_fits[B]
 
     def _step_prologue(self, s: "_Step"):
         """What precedes the forward: the decoder's image of a trainable E, the annealed beta, and the placement of
@@ -962,9 +1009,10 @@ class FusedTrainer:
         check(lib().hvae_adam_lazy_catchup(*self._lazy_w1(), rg_ref, self.layout.n_items, self.layout.hidden[0],
                                            st), "adam_lazy_catchup")
 
-    def _apply_pending(self, sweep_rows: int, st):
-        check(lib().hvae_adam_lazy_pending(*self._lazy_w1(), self.layout.n_items, self.layout.hidden[0], sweep_rows,
-                                           C.byref(self._pend), st), "adam_lazy_pending")
+    def _apply_pending(self, sweep_rows: int, st, guest: bool = False):
+        fn = lib().hvae_adam_lazy_pending_guest if guest else lib().hvae_adam_lazy_pending
+        check(fn(*self._lazy_w1(), self.layout.n_items, self.layout.hidden[0], sweep_rows, C.byref(self._pend), st),
+              "adam_lazy_pending_guest" if guest else "adam_lazy_pending")
 
     def flush(self):
         """Bring every W1t row (and its m, v) up to the completed step count (lazy Adam). Called at the end of every
