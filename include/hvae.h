@@ -873,6 +873,54 @@ int hvae_mvae_tanh_drop_bwd(const float* dh, int64_t ldd, const float* t, int64_
 int hvae_mvae_nll(const hvae_csr_batch* x, float* S, int64_t lds, float grad_scale, float* lse, float* recon_rows,
                   void* stream);
 
+/* ----------------------------------------------------------- t-SNE (K21) -- */
+/* The latent-space figure's t-SNE (plot_latent_space, src/ml/visualize.py:163-289: scikit-learn's TSNE with
+ * method="barnes_hut", init="pca", learning_rate="auto") with the exact O(n^2) repulsion in place of the tree (its
+ * angle = 0 limit) and every quantity in fp64. Served: HVAE_TSNE_MIN_N <= n <= HVAE_TSNE_MAX_N points of
+ * HVAE_TSNE_MIN_L <= L <= HVAE_TSNE_MAX_L columns, k = min(n - 1, int(3 perplexity + 1)) <= HVAE_TSNE_MAX_K
+ * neighbours, perplexity < n; anything else is HVAE_ERR_ARG before any launch. No atomics; every sum has one fixed
+ * order that depends on the shapes only (csrc/hvae_tsne.hip states each), so two fits give the same bits. The caller
+ * owns every buffer and the stream; nothing here allocates or waits. An embedding is [n, 2] doubles, 16-byte aligned.
+ *
+ * hvae_tsne_knn: for each row of X (fp32 [n, L], row stride ldx) its k nearest other rows by the squared distance
+ * sum_l (double(x_il) - double(x_jl))^2, sorted ascending by (distance, index): idx int32 [n, k], d2 double [n, k].
+ * Duplicated rows are ordinary input (distance exactly 0, smaller index first). A row with NaN entries gets index -1.
+ * One block of 256 threads per row, at most 1024 blocks; ws holds hvae_tsne_knn_workspace(n) bytes (one row of n
+ * distances per block), 8-byte aligned. */
+#define HVAE_TSNE_MIN_N 33
+#define HVAE_TSNE_MAX_N 16384
+#define HVAE_TSNE_MIN_L 4
+#define HVAE_TSNE_MAX_L 1024
+#define HVAE_TSNE_MAX_K 255
+size_t hvae_tsne_knn_workspace(int64_t n);
+int hvae_tsne_knn(const float* X, int64_t n, int64_t L, int64_t ldx, int64_t k, int32_t* idx, double* d2, void* ws,
+                  size_t ws_bytes, void* stream);
+/* The conditional P [n, k] of d2 [n, k]: scikit-learn's _binary_search_perplexity loop per row (beta from 1, at most
+ * 100 steps, H = log sum P + beta sum d P / sum P, stop at |H - log perplexity| <= 1e-5, else double / halve / take
+ * the midpoint; sum P = 0 is replaced by 1e-8). One wave per row, four rows per block. P may not alias d2. */
+int hvae_tsne_perplexity(const double* d2, int64_t n, int64_t k, double perplexity, double* P, void* stream);
+/* One force evaluation at Y over the symmetric joint P as a CSR (ptr int64 [n + 1], col int32, pval double), with
+ * q_ij = 1 / (1 + |y_i - y_j|^2):
+ *   attr[i] = sum_{j in row i} p_ij q_ij (y_i - y_j)     rep[i] = sum_{j != i} q_ij^2 (y_i - y_j)
+ *   z[i]    = sum_{j != i} q_ij
+ * attr and rep are [n, 2], z is [n]. Coincident points give q = 1 and no force; a column outside [0, n) gives NaN in
+ * its row, never a read out of bounds. 16 points per block of 256 threads, 16 threads per point. */
+int hvae_tsne_forces(const double* Y, int64_t n, const int64_t* ptr, const int32_t* col, const double* pval,
+                     double* attr, double* rep, double* z, void* stream);
+/* Z = max(sum_i z[i], DBL_EPSILON); grad = 4 (exaggeration attr - rep / Z); then scikit-learn's _gradient_descent
+ * step per coordinate: gains += 0.2 where update grad < 0, else gains *= 0.8, floor 0.01; grad *= gains;
+ * update = momentum update - lr grad; y_out = y_in + update (y_out may not alias y_in). gains and upd are [n, 2] and
+ * updated in place. With want_stats != 0 also stats[0] = sum_ij p log(max(p, FLT_MIN) / max(q_ij / Z, FLT_MIN)) over
+ * the stored entries at y_in with p = exaggeration p_ij, and stats[1] = ||grad||_2 after the gains; ptr, col, pval,
+ * stats and ws (hvae_tsne_update_workspace(n) bytes, 8-byte aligned) are read only then. grad_out (nullable, [n, 2])
+ * receives the gradient before the gains, z_out (nullable, one double) receives Z. One thread per point; a second,
+ * one-thread launch adds the blocks' partial statistics in block order. */
+size_t hvae_tsne_update_workspace(int64_t n);
+int hvae_tsne_update(const double* attr, const double* rep, const double* z, int64_t n, double exaggeration,
+                     double momentum, double lr, double* gains, double* upd, const double* y_in, double* y_out,
+                     const int64_t* ptr, const int32_t* col, const double* pval, int want_stats, double* stats,
+                     double* grad_out, double* z_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and
  * released by hvae_host_csr_free. */

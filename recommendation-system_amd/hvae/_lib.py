@@ -143,6 +143,8 @@ class LgcnGraph(C.Structure):  # hvae_lgcn_graph
 
 LGCN_MAX_BATCH = 1024  # include/hvae.h HVAE_LGCN_MAX_BATCH
 SVD_LD = 64            # include/hvae.h HVAE_SVD_LD
+# include/hvae.h HVAE_TSNE_*: the served range of the t-SNE kernels
+TSNE_MIN_N, TSNE_MAX_N, TSNE_MIN_L, TSNE_MAX_L, TSNE_MAX_K = 33, 16384, 4, 1024, 255
 
 P = C.POINTER
 # name ->(restype, argtypes); mirrors include/hvae.h one to one.
@@ -241,6 +243,13 @@ SIGNATURES = {
     "hvae_svd_gram": (cint, [vp, i64, i64, vp, vp, sz, vp]),
     "hvae_svd_chol_inv": (cint, [vp, i64, vp, vp, vp]),
     "hvae_svd_apply": (cint, [vp, i64, i64, vp, i64, vp, vp]),
+    "hvae_tsne_knn_workspace": (sz, [i64]),
+    "hvae_tsne_knn": (cint, [vp, i64, i64, i64, i64, vp, vp, vp, sz, vp]),
+    "hvae_tsne_perplexity": (cint, [vp, i64, i64, f64, vp, vp]),
+    "hvae_tsne_forces": (cint, [vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "hvae_tsne_update_workspace": (sz, [i64]),
+    "hvae_tsne_update": (cint, [vp, vp, vp, i64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, cint, vp, vp, vp, vp, sz,
+                                vp]),
     "hvae_mvae_encoder_fwd": (cint, [P(CsrBatch), vp, vp, i64, f32, f32, vp, vp, u64, vp, cint, vp, vp, vp, vp]),
     "hvae_mvae_tanh_drop_fwd": (cint, [vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, vp, i64, vp]),
     "hvae_mvae_tanh_drop_bwd": (cint, [vp, i64, vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, i64, vp]),

@@ -998,3 +998,155 @@ def mvae_nll(x: Csr, S: torch.Tensor, grad_scale: float, lse=None, recon_rows=No
     check(lib().hvae_mvae_nll(x.ref, ptr(S), S.stride(0), float(grad_scale), ptr(lse), ptr(recon_rows),
                               stream_of(S)), "hvae_mvae_nll")
     return lse, recon_rows
+
+
+# -------------------------------------------------------------------- t-SNE --
+TSNE_SERVED = (f"served: {_lib.TSNE_MIN_N} <= n <= {_lib.TSNE_MAX_N} points of {_lib.TSNE_MIN_L} <= L <= "
+               f"{_lib.TSNE_MAX_L} columns, 0 < perplexity < n, k = min(n - 1, int(3 * perplexity + 1)) <= "
+               f"{_lib.TSNE_MAX_K} neighbours")
+
+
+def tsne_neighbours(n: int, L: int | None, perplexity: float, what: str = "tsne") -> int:
+    """k = min(n - 1, int(3 * perplexity + 1)), scikit-learn's neighbour count, for a served shape; a ValueError that
+    names the served range otherwise (before any launch)."""
+    n, perplexity = int(n), float(perplexity)
+    if not _lib.TSNE_MIN_N <= n <= _lib.TSNE_MAX_N:
+        raise ValueError(f"{what}: n = {n} points is not served; {TSNE_SERVED}")
+    if L is not None and not _lib.TSNE_MIN_L <= int(L) <= _lib.TSNE_MAX_L:
+        raise ValueError(f"{what}: L = {L} columns is not served; {TSNE_SERVED}")
+    if not 0.0 < perplexity < n:
+        raise ValueError(f"{what}: perplexity = {perplexity} with n = {n} is not served; {TSNE_SERVED}")
+    k = min(n - 1, int(3.0 * perplexity + 1))
+    if not 1 <= k <= _lib.TSNE_MAX_K:
+        raise ValueError(f"{what}: perplexity = {perplexity} needs k = {k} neighbours, which is not served; "
+                         f"{TSNE_SERVED}")
+    return k
+
+
+def _tsne_mat(what: str, name: str, t: torch.Tensor, n: int, w: int, dtype=torch.float64):
+    require_hip(t)
+    if t.dtype != dtype or t.dim() != 2 or tuple(t.shape) != (n, w) or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} [{n}, {w}] matrix, got {tuple(t.shape)} "
+                         f"{t.dtype} with strides {tuple(t.stride())}")
+
+
+def tsne_knn(X: torch.Tensor, perplexity: float):
+    """The k = min(n - 1, int(3 perplexity + 1)) nearest other rows of each row of X (fp32 [n, L], unit column
+    stride) by squared Euclidean distance in fp64 (hvae_tsne_knn) -> (idx int32 [n, k], d2 float64 [n, k]), each row
+    ascending by (distance, index)."""
+    if X.dim() != 2:
+        raise ValueError(f"tsne_knn: X must be a float32 [n, L] matrix, got {tuple(X.shape)}; {TSNE_SERVED}")
+    n, L = X.shape
+    k = tsne_neighbours(n, L, perplexity, "tsne_knn")
+    require_hip(X)
+    if X.dtype != torch.float32 or X.stride(1) != 1 or X.stride(0) < L:
+        raise ValueError(f"tsne_knn: X must be float32 with unit column stride, got {X.dtype} with strides "
+                         f"{tuple(X.stride())}")
+    idx = torch.empty(n, k, dtype=torch.int32, device=X.device)
+    d2 = torch.empty(n, k, dtype=torch.float64, device=X.device)
+    ws = workspace(X.device, lib().hvae_tsne_knn_workspace(n))
+    check(lib().hvae_tsne_knn(ptr(X), n, L, X.stride(0), k, ptr(idx), ptr(d2), ptr(ws), ws.numel(), stream_of(X)),
+          "hvae_tsne_knn")
+    return idx, d2
+
+
+def tsne_perplexity(d2: torch.Tensor, perplexity: float) -> torch.Tensor:
+    """The conditional P [n, k] of the neighbour distances d2 [n, k]: scikit-learn's binary search for the
+    perplexity, one row per wave (hvae_tsne_perplexity)."""
+    if d2.dim() != 2:
+        raise ValueError(f"tsne_perplexity: d2 must be a float64 [n, k] matrix, got {tuple(d2.shape)}")
+    n, k = d2.shape
+    if k != tsne_neighbours(n, None, perplexity, "tsne_perplexity"):
+        raise ValueError(f"tsne_perplexity: d2 holds {k} neighbours per row, perplexity = {perplexity} takes "
+                         f"{tsne_neighbours(n, None, perplexity)}; {TSNE_SERVED}")
+    _tsne_mat("tsne_perplexity", "d2", d2, n, k)
+    P = torch.empty_like(d2)
+    check(lib().hvae_tsne_perplexity(ptr(d2), n, k, float(perplexity), ptr(P), stream_of(d2)), "hvae_tsne_perplexity")
+    return P
+
+
+class TsneP:
+    """The symmetric joint P as a device CSR with sorted columns: ptr int64 [n + 1], col int32, val float64."""
+
+    def __init__(self, row_ptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor):
+        require_hip(row_ptr, col, val)
+        if row_ptr.dtype != torch.int64 or col.dtype != torch.int32 or val.dtype != torch.float64 \
+                or col.numel() != val.numel():
+            raise ValueError("TsneP: ptr int64, col int32 and val float64 of equal length are needed")
+        self.ptr, self.col, self.val, self.n = row_ptr, col, val, row_ptr.numel() - 1
+
+    def to_scipy(self):
+        from scipy.sparse import csr_matrix
+        return csr_matrix((self.val.cpu().numpy(), self.col.cpu().numpy(), self.ptr.cpu().numpy()),
+                          shape=(self.n, self.n))
+
+
+def tsne_joint(idx: torch.Tensor, cond: torch.Tensor) -> TsneP:
+    """P = (P_cond + P_cond^T) / max(sum, eps) as a CSR with sorted columns: the fit's one host step (scipy on the
+    downloaded [n, k] arrays, one upload), as scikit-learn's _joint_probabilities_nn forms it."""
+    import numpy as np
+    from scipy.sparse import csr_matrix
+    idx_h, c = idx.cpu().numpy(), cond.cpu().numpy()
+    n, k = idx_h.shape
+    if idx_h.min() < 0 or not np.isfinite(c).all():
+        raise ValueError("tsne_joint: the input holds non-finite values (a row found fewer than k neighbours)")
+    P = csr_matrix((c.ravel(), idx_h.ravel(), np.arange(0, n * k + 1, k)), shape=(n, n))
+    P.sort_indices()
+    P = P + P.T
+    P /= np.maximum(P.sum(), np.finfo(np.double).eps)
+    P.sort_indices()
+    dev = idx.device
+    return TsneP(torch.as_tensor(P.indptr.astype(np.int64), device=dev),
+                 torch.as_tensor(P.indices.astype(np.int32), device=dev),
+                 torch.as_tensor(P.data.astype(np.float64), device=dev))
+
+
+def tsne_forces(Y: torch.Tensor, P: TsneP, attr=None, rep=None, z=None):
+    """One force evaluation at the embedding Y [n, 2] (hvae_tsne_forces) -> (attr [n, 2], rep [n, 2], z [n])."""
+    if Y.dim() != 2:
+        raise ValueError(f"tsne_forces: Y must be a float64 [n, 2] matrix, got {tuple(Y.shape)}")
+    n = Y.shape[0]
+    if not _lib.TSNE_MIN_N <= n <= _lib.TSNE_MAX_N or P.n != n:
+        raise ValueError(f"tsne_forces: n = {n} points (P holds {P.n} rows) is not served; {TSNE_SERVED}")
+    _tsne_mat("tsne_forces", "Y", Y, n, 2)
+    attr = torch.empty_like(Y) if attr is None else attr
+    rep = torch.empty_like(Y) if rep is None else rep
+    z = torch.empty(n, dtype=torch.float64, device=Y.device) if z is None else z
+    _tsne_mat("tsne_forces", "attr", attr, n, 2)
+    _tsne_mat("tsne_forces", "rep", rep, n, 2)
+    _tsne_mat("tsne_forces", "z", z.view(n, 1) if z.dim() == 1 else z, n, 1)
+    check(lib().hvae_tsne_forces(ptr(Y), n, ptr(P.ptr), ptr(P.col), ptr(P.val), ptr(attr), ptr(rep), ptr(z),
+                                 stream_of(Y)), "hvae_tsne_forces")
+    return attr, rep, z
+
+
+def tsne_update(attr, rep, z, gains, upd, y_in, y_out, exaggeration: float, momentum: float, lr: float,
+                P: TsneP | None = None, stats: torch.Tensor | None = None, grad_out=None, z_out=None):
+    """scikit-learn's gradient-descent step from one force evaluation (hvae_tsne_update): gains and upd in place,
+    y_out = y_in + update. With stats (float64 [2], device; P is then needed) it receives the KL error at y_in and
+    the gradient norm after the gains; grad_out [n, 2] receives the gradient before the gains, z_out [1] receives Z."""
+    n = y_in.shape[0]
+    if not _lib.TSNE_MIN_N <= n <= _lib.TSNE_MAX_N:
+        raise ValueError(f"tsne_update: n = {n} points is not served; {TSNE_SERVED}")
+    for name, t in (("attr", attr), ("rep", rep), ("gains", gains), ("upd", upd), ("y_in", y_in), ("y_out", y_out)):
+        _tsne_mat("tsne_update", name, t, n, 2)
+    if grad_out is not None:
+        _tsne_mat("tsne_update", "grad_out", grad_out, n, 2)
+    _tsne_mat("tsne_update", "z", z.view(n, 1), n, 1)
+    if y_in.data_ptr() == y_out.data_ptr():
+        raise ValueError("tsne_update: y_out may not alias y_in")
+    want = stats is not None
+    ws = None
+    if want:
+        if P is None or P.n != n or stats.dtype != torch.float64 or stats.numel() != 2:
+            raise ValueError("tsne_update: the statistics need P over the same n points and a float64 [2] stats")
+        require_hip(stats)
+        ws = workspace(y_in.device, lib().hvae_tsne_update_workspace(n))
+    if z_out is not None and (z_out.dtype != torch.float64 or z_out.numel() != 1):
+        raise ValueError("tsne_update: z_out must be one float64")
+    check(lib().hvae_tsne_update(ptr(attr), ptr(rep), ptr(z), n, float(exaggeration), float(momentum), float(lr),
+                                 ptr(gains), ptr(upd), ptr(y_in), ptr(y_out), ptr(P.ptr) if want else None,
+                                 ptr(P.col) if want else None, ptr(P.val) if want else None, int(want), ptr(stats),
+                                 ptr(grad_out), ptr(z_out), ptr(ws), ws.numel() if want else 0, stream_of(y_in)),
+          "hvae_tsne_update")
+    return y_out
