@@ -15,18 +15,12 @@
 // Everything is fp32 with no floating-point atomics; every sum has one fixed order that depends on the graph
 // (or the batch plan) only, so two runs are bitwise equal.
 //
-// Summation order of a propagated row. A wave owns the row, lane l owns columns [l V, l V + V) (V = d / 64), so
-// a neighbour row is one coalesced 256-byte (d = 64) or 512-byte (d = 128) read. The neighbour list is walked in
-// storage order in chunks of 64 (lane l fetches index and weight of entry l, then they are broadcast); within a
-// chunk entry k goes to accumulator k mod 4 while four entries are left and to accumulator 0 after that; the row
-// sum is (a0 + a1) + (a2 + a3). A row longer than kLgcnSplit is cut into four contiguous quarters, one per wave
-// of the block, each summed as above, and merged ((q0 + q1) + q2) + q3 through LDS.
-#include "hvae_common.h"
+// A propagated row is a gathered row sum of hvae_rowgather.h, whose first comment states its summation order: lane
+// l owns columns [l V, l V + V) (V = d / 64), so a neighbour row is one coalesced 256-byte (d = 64) or 512-byte
+// (d = 128) read.
+#include "hvae_rowgather.h"
 
 namespace hvae {
-
-constexpr int kLgcnRows = 4;       // rows per 256-thread block: one wave each
-constexpr int kLgcnSplit = 256;    // neighbours above which the block's four waves share one row
 
 __global__ void __launch_bounds__(256) k_lgcn_norm(const int64_t* __restrict__ row_ptr, int64_t n_users,
                                                    const int64_t* __restrict__ col_ptr, int64_t n_items,
@@ -37,77 +31,9 @@ __global__ void __launch_bounds__(256) k_lgcn_norm(const int64_t* __restrict__ r
   scale[i] = deg > 0 ? 1.0 / sqrt((double)deg) : 0.0;
 }
 
-template <int V>
-struct RowVec {
-  float v[V];
-};
-template <int V>
-__device__ __forceinline__ RowVec<V> ld_row(const float* __restrict__ t, int64_t row, int lane) {
-  RowVec<V> r;
-  const float* p = t + row * (64 * V) + lane * V;
-  if constexpr (V == 2) {
-    const float2 x = *reinterpret_cast<const float2*>(p);
-    r.v[0] = x.x;
-    r.v[1] = x.y;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-template <int V>
-__device__ __forceinline__ void st_row(float* __restrict__ t, int64_t row, int lane, const RowVec<V>& r) {
-  float* p = t + row * (64 * V) + lane * V;
-  if constexpr (V == 2) *reinterpret_cast<float2*>(p) = make_float2(r.v[0], r.v[1]);
-  else *p = r.v[0];
-}
-template <int V>
-__device__ __forceinline__ void fma_row(RowVec<V>& acc, float w, const RowVec<V>& x) {
-#pragma unroll
-  for (int v = 0; v < V; ++v) acc.v[v] = fmaf(w, x.v[v], acc.v[v]);
-}
-__device__ __forceinline__ float bcast_f(float x, int k) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), k));
-}
-
-// sum_{p in [p0, p1)} w(r, idx[p] + off) x[idx[p] + off] for one wave; neighbours outside [lo, hi) (a broken
-// graph) read row lo with a NaN weight instead of reading out of bounds.
-template <int V>
-__device__ __forceinline__ RowVec<V> lgcn_span(const int32_t* __restrict__ idx, int64_t p0, int64_t p1, int64_t off,
-                                               int64_t lo, int64_t hi, double s_r, const double* __restrict__ scale,
-                                               const float* __restrict__ x, int lane) {
-  RowVec<V> a[4] = {};
-  for (int64_t base = p0; base < p1; base += 64) {
-    const int cnt = (int)(p1 - base < 64 ? p1 - base : 64);
-    int jv = (int)lo;
-    float wv = 0.f;
-    if (lane < cnt) {
-      const int64_t j = (int64_t)idx[base + lane] + off;
-      if (j >= lo && j < hi) {
-        jv = (int)j;
-        wv = (float)(s_r * scale[j]);
-      } else {
-        wv = NAN;
-      }
-    }
-    int k = 0;
-    for (; k + 4 <= cnt; k += 4) {
-      const int j0 = __builtin_amdgcn_readlane(jv, k), j1 = __builtin_amdgcn_readlane(jv, k + 1);
-      const int j2 = __builtin_amdgcn_readlane(jv, k + 2), j3 = __builtin_amdgcn_readlane(jv, k + 3);
-      const RowVec<V> x0 = ld_row<V>(x, j0, lane), x1 = ld_row<V>(x, j1, lane);
-      const RowVec<V> x2 = ld_row<V>(x, j2, lane), x3 = ld_row<V>(x, j3, lane);
-      fma_row<V>(a[0], bcast_f(wv, k), x0);
-      fma_row<V>(a[1], bcast_f(wv, k + 1), x1);
-      fma_row<V>(a[2], bcast_f(wv, k + 2), x2);
-      fma_row<V>(a[3], bcast_f(wv, k + 3), x3);
-    }
-    for (; k < cnt; ++k) fma_row<V>(a[0], bcast_f(wv, k), ld_row<V>(x, __builtin_amdgcn_readlane(jv, k), lane));
-  }
-  RowVec<V> s;
-#pragma unroll
-  for (int v = 0; v < V; ++v) s.v[v] = (a[0].v[v] + a[1].v[v]) + (a[2].v[v] + a[3].v[v]);
-  return s;
-}
-
+// out[r] = alpha * (add[r] + sum_{j in N(r)} w_rj x[j]) with w_rj = (float)(s_r * s_j); a user row's neighbours are
+// col_idx + n_users, an item row's row_idx. A neighbour outside the other side's node range (a broken graph) reads
+// that range's first row with a NaN weight instead of reading out of bounds.
 template <int V>
 __global__ void __launch_bounds__(256) k_lgcn_propagate(const int64_t* __restrict__ row_ptr,
                                                         const int32_t* __restrict__ col_idx,
@@ -116,54 +42,36 @@ __global__ void __launch_bounds__(256) k_lgcn_propagate(const int64_t* __restric
                                                         const double* __restrict__ scale, int64_t n_users,
                                                         int64_t n_items, const float* __restrict__ x,
                                                         const float* add, float* out, float alpha) {
-  constexpr int D = 64 * V;
-  __shared__ float part[kLgcnRows][D];
+  using Row = RowVec<float, V>;
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t n = n_users + n_items;
-  const int64_t r0 = (int64_t)blockIdx.x * kLgcnRows;
-  for (int q = 0; q < kLgcnRows; ++q) {  // every wave looks at the block's rows: a long one is shared
-    const int64_t r = r0 + q;
-    if (r >= n) break;
-    const bool is_user = r < n_users;
-    const int64_t* ptr = is_user ? row_ptr + r : col_ptr + (r - n_users);
-    const int32_t* idx = is_user ? col_idx : row_idx;
-    const int64_t p0 = ptr[0], p1 = ptr[1];
-    const int64_t off = is_user ? n_users : 0, lo = is_user ? n_users : 0, hi = is_user ? n : n_users;
-    const int64_t deg = p1 - p0;
-    const bool split = deg > kLgcnSplit;  // the same in every wave of the block
-    if (!split && q != wave) continue;
-    int64_t a = p0, b = p1;
-    if (split) {
-      const int64_t per = (deg + kLgcnRows - 1) / kLgcnRows;
-      a = p0 + wave * per;
-      if (a > p1) a = p1;
-      b = a + per < p1 ? a + per : p1;
-    }
-    RowVec<V> s = lgcn_span<V>(idx, a, b, off, lo, hi, scale[r], scale, x, lane);
-    if (split) {
+  gather_rows<float, V>(
+      n, true,
+      [&](int64_t r, int64_t& p0, int64_t& p1) {
+        const bool is_user = r < n_users;
+        const int64_t* ptr = is_user ? row_ptr + r : col_ptr + (r - n_users);
+        const int32_t* idx = is_user ? col_idx : row_idx;
+        p0 = ptr[0];
+        p1 = ptr[1];
+        const int64_t off = is_user ? n_users : 0, lo = is_user ? n_users : 0, hi = is_user ? n : n_users;
+        const double s_r = scale[r];
+        return [=](int64_t p) {
+          const int64_t j = (int64_t)idx[p] + off;
+          return j >= lo && j < hi ? GatherEntry<float>{(int)j, (float)(s_r * scale[j])}
+                                   : GatherEntry<float>{(int)lo, NAN};
+        };
+      },
+      [&](int j) { return ld_row<float, V>(x, j, lane); },
+      [&](int64_t r, Row s) {
+        if (add) {
+          const Row e = ld_row<float, V>(add, r, lane);
 #pragma unroll
-      for (int v = 0; v < V; ++v) part[wave][lane * V + v] = s.v[v];
-      __syncthreads();
-      if (wave == 0) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) {
-          const int c = lane * V + v;
-          s.v[v] = ((part[0][c] + part[1][c]) + part[2][c]) + part[3][c];
+          for (int v = 0; v < V; ++v) s.v[v] = e.v[v] + s.v[v];
         }
-      }
-      __syncthreads();
-      if (wave != 0) continue;
-    }
-    if (add) {
-      const RowVec<V> e = ld_row<V>(add, r, lane);
 #pragma unroll
-      for (int v = 0; v < V; ++v) s.v[v] = e.v[v] + s.v[v];
-    }
-#pragma unroll
-    for (int v = 0; v < V; ++v) s.v[v] = alpha * s.v[v];
-    st_row<V>(out, r, lane, s);
-  }
+        for (int v = 0; v < V; ++v) s.v[v] = alpha * s.v[v];
+        st_row<float, V>(out, r, lane, s);
+      });
 }
 
 // ---- BPR -------------------------------------------------------------------------------------------------
@@ -187,7 +95,8 @@ __global__ void __launch_bounds__(256) k_lgcn_bpr_rows(const float* __restrict__
     if (lane == 0) { coef[b] = NAN; sp[b] = NAN; sq[b] = NAN; }
     return;
   }
-  const RowVec<V> fu = ld_row<V>(F, u, lane), fp = ld_row<V>(F, n_users + p, lane), fn = ld_row<V>(F, n_users + q, lane);
+  const RowVec<float, V> fu = ld_row<float, V>(F, u, lane), fp = ld_row<float, V>(F, n_users + p, lane),
+                         fn = ld_row<float, V>(F, n_users + q, lane);
   float dp = 0.f, dn = 0.f, nn = 0.f;
 #pragma unroll
   for (int v = 0; v < V; ++v) {
@@ -253,7 +162,7 @@ __global__ void __launch_bounds__(256) k_lgcn_bpr_grad(const float* __restrict__
   const int64_t n = n_users + n_items;
   if (e0 < 0 || e1 <= e0 || e1 > 3 * nb) return;  // a broken plan writes nothing
   int64_t node = -1;
-  RowVec<V> acc = {}, self = {};
+  RowVec<float, V> acc = {}, self = {};
   bool bad = false;
   for (int64_t base = e0; base < e1; base += 64) {
     const int cnt = (int)(e1 - base < 64 ? e1 - base : 64);
@@ -281,13 +190,13 @@ __global__ void __launch_bounds__(256) k_lgcn_bpr_grad(const float* __restrict__
       if (m < 0 || (node >= 0 && m != node)) { bad = true; continue; }
       if (node < 0) {
         node = m;
-        self = ld_row<V>(F, node, lane);
+        self = ld_row<float, V>(F, node, lane);
       }
-      const float c = bcast_f(ca, k);
-      fma_row<V>(acc, c, ld_row<V>(F, __builtin_amdgcn_readlane(ia, k), lane));
+      const float c = bcast(ca, k);
+      fma_row<float, V>(acc, c, ld_row<float, V>(F, __builtin_amdgcn_readlane(ia, k), lane));
       const int j = __builtin_amdgcn_readlane(ib, k);
-      if (j >= 0) fma_row<V>(acc, -c, ld_row<V>(F, j, lane));
-      fma_row<V>(acc, r2, self);
+      if (j >= 0) fma_row<float, V>(acc, -c, ld_row<float, V>(F, j, lane));
+      fma_row<float, V>(acc, r2, self);
     }
   }
   if (node < 0 || node >= n) return;
@@ -295,7 +204,7 @@ __global__ void __launch_bounds__(256) k_lgcn_bpr_grad(const float* __restrict__
 #pragma unroll
     for (int v = 0; v < V; ++v) acc.v[v] = NAN;
   }
-  st_row<V>(g, node, lane, acc);
+  st_row<float, V>(g, node, lane, acc);
 }
 
 }  // namespace hvae
@@ -322,7 +231,7 @@ extern "C" int hvae_lgcn_propagate(const hvae_lgcn_graph* gr, int64_t d, const f
   HVAE_REQUIRE(gr->row_ptr && gr->col_idx && gr->col_ptr && gr->row_idx && gr->scale && x && out,
                "hvae_lgcn_propagate: null pointer");
   HVAE_REQUIRE(x != out, "hvae_lgcn_propagate: out may not alias x");
-  const unsigned grid = (unsigned)cdiv(gr->n_users + gr->n_items, kLgcnRows);
+  const unsigned grid = (unsigned)cdiv(gr->n_users + gr->n_items, kGatherRows);
   hipStream_t st = as_stream(stream);
   if (d == 64)
     k_lgcn_propagate<1><<<grid, 256, 0, st>>>(gr->row_ptr, gr->col_idx, gr->col_ptr, gr->row_idx, gr->scale,

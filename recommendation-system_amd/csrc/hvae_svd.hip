@@ -12,100 +12,38 @@
 // gathered reads, not by the FMA rate) with no atomics; every sum has one fixed order that depends on the shapes
 // only, so two runs are bitwise equal.
 //
-// Summation order of an spmm row. A wave owns the row, lane l owns column l, so a gathered row of X is one coalesced
-// 512-byte read. The entries are walked in storage order in chunks of 64 (lane l fetches index and value of entry l,
-// then they are broadcast); within a chunk entry k goes to accumulator k mod 4 while four entries are left and to
-// accumulator 0 after that; the row sum is (a0 + a1) + (a2 + a3). A row longer than kSvdSplit is cut into four
-// contiguous quarters, one per wave of the block, each summed as above, and merged ((q0 + q1) + q2) + q3 through LDS.
-#include "hvae_common.h"
+// An spmm row is a gathered row sum of hvae_rowgather.h, whose first comment states its summation order: lane l owns
+// column l, so a gathered row of X is one coalesced 512-byte read.
+#include "hvae_rowgather.h"
 
 namespace hvae {
 
 constexpr int kSvdLd = HVAE_SVD_LD;
-constexpr int kSvdRows = 4;         // spmm / apply rows per 256-thread block: one wave each
-constexpr int kSvdSplit = 256;      // entries above which the block's four waves share one spmm row
+constexpr int kApplyRows = 4;       // apply rows per 256-thread block: one wave each
 constexpr int kGramRows = 32;       // rows of Y staged per step of a gram block
 constexpr int kGramMaxBlocks = 256; // partial Gram matrices at the most
 static_assert(kSvdLd == 64, "one lane per column");
 
-__device__ __forceinline__ double bcast_d(double x, int k) {
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, k);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), k);
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// sum_{p in [p0, p1)} double(vals[p]) x[idx[p], lane] for one wave; an index outside [0, n_cols) (a broken matrix)
-// reads row 0 with a NaN weight instead of reading out of bounds. Lanes from W up read nothing and return 0.
-__device__ __forceinline__ double svd_span(const int32_t* __restrict__ idx, const float* __restrict__ vals,
-                                           int64_t p0, int64_t p1, int64_t n_cols, const double* __restrict__ x,
-                                           int lane, bool live) {
-  double a[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t base = p0; base < p1; base += 64) {
-    const int cnt = (int)(p1 - base < 64 ? p1 - base : 64);
-    int jv = 0;
-    double wv = 0.0;
-    if (lane < cnt) {
-      const int64_t j = idx[base + lane];
-      if (j >= 0 && j < n_cols) {
-        jv = (int)j;
-        wv = (double)vals[base + lane];
-      } else {
-        wv = NAN;
-      }
-    }
-    int k = 0;
-    for (; k + 4 <= cnt; k += 4) {
-      const int64_t j0 = __builtin_amdgcn_readlane(jv, k), j1 = __builtin_amdgcn_readlane(jv, k + 1);
-      const int64_t j2 = __builtin_amdgcn_readlane(jv, k + 2), j3 = __builtin_amdgcn_readlane(jv, k + 3);
-      const double x0 = live ? x[j0 * kSvdLd + lane] : 0.0, x1 = live ? x[j1 * kSvdLd + lane] : 0.0;
-      const double x2 = live ? x[j2 * kSvdLd + lane] : 0.0, x3 = live ? x[j3 * kSvdLd + lane] : 0.0;
-      a[0] = fma(bcast_d(wv, k), x0, a[0]);
-      a[1] = fma(bcast_d(wv, k + 1), x1, a[1]);
-      a[2] = fma(bcast_d(wv, k + 2), x2, a[2]);
-      a[3] = fma(bcast_d(wv, k + 3), x3, a[3]);
-    }
-    for (; k < cnt; ++k) {
-      const int64_t j = __builtin_amdgcn_readlane(jv, k);
-      a[0] = fma(bcast_d(wv, k), live ? x[j * kSvdLd + lane] : 0.0, a[0]);
-    }
-  }
-  return live ? (a[0] + a[1]) + (a[2] + a[3]) : 0.0;
-}
-
+// out[r, lane] = sum_p double(vals[p]) x[idx[p], lane] over row r's entries; an index outside [0, n_cols) (a broken
+// matrix) reads row 0 with a NaN weight instead of reading out of bounds. Lanes from W up read nothing and write 0.
 __global__ void __launch_bounds__(256) k_svd_spmm(const int64_t* __restrict__ ptr, const int32_t* __restrict__ idx,
                                                   const float* __restrict__ vals, int64_t n_rows, int64_t n_cols,
                                                   const double* __restrict__ x,
                                                   double* __restrict__ out, int W) {
-  __shared__ double part[kSvdRows][kSvdLd];
+  using Row = RowVec<double, 1>;
   const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const bool live = lane < W;
-  const int64_t r0 = (int64_t)blockIdx.x * kSvdRows;
-  for (int q = 0; q < kSvdRows; ++q) {  // every wave looks at the block's rows: a long one is shared
-    const int64_t r = r0 + q;
-    if (r >= n_rows) break;
-    const int64_t p0 = ptr[r], p1 = ptr[r + 1];
-    const int64_t deg = p1 - p0;
-    const bool split = deg > kSvdSplit;  // the same in every wave of the block
-    if (!split && q != wave) continue;
-    int64_t a = p0, b = p1;
-    if (split) {
-      const int64_t per = (deg + kSvdRows - 1) / kSvdRows;
-      a = p0 + wave * per;
-      if (a > p1) a = p1;
-      b = a + per < p1 ? a + per : p1;
-    }
-    double s = svd_span(idx, vals, a, b, n_cols, x, lane, live);
-    if (split) {
-      part[wave][lane] = s;
-      __syncthreads();
-      if (wave == 0) s = ((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane];
-      __syncthreads();
-      if (wave != 0) continue;
-    }
-    out[r * kSvdLd + lane] = s;
-  }
+  gather_rows<double, 1>(
+      n_rows, lane < W,
+      [&](int64_t r, int64_t& p0, int64_t& p1) {
+        p0 = ptr[r];
+        p1 = ptr[r + 1];
+        return [&](int64_t p) {
+          const int64_t j = idx[p];
+          return j >= 0 && j < n_cols ? GatherEntry<double>{(int)j, (double)vals[p]} : GatherEntry<double>{0, NAN};
+        };
+      },
+      [&](int j) { return ld_row<double, 1>(x, j, lane); },
+      [&](int64_t r, const Row& s) { out[r * kSvdLd + lane] = s.v[0]; });
 }
 
 // ---- Gram ------------------------------------------------------------------------------------------------
@@ -220,15 +158,15 @@ __global__ void __launch_bounds__(256) k_svd_chol_inv(const double* __restrict__
 __global__ void __launch_bounds__(256) k_svd_apply(const double* Y, int64_t n, int W, const double* __restrict__ T,
                                                    int W_out, double* out) {
   __shared__ double tm[kSvdLd][kSvdLd];
-  __shared__ double yrow[kSvdRows][kSvdLd];
+  __shared__ double yrow[kApplyRows][kSvdLd];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int e = threadIdx.x; e < kSvdLd * kSvdLd; e += 256) {
     const int i = e >> 6, j = e & 63;
     tm[i][j] = (i < W && j < W_out) ? T[e] : 0.0;
   }
-  const int64_t n_groups = (n + kSvdRows - 1) / kSvdRows;
+  const int64_t n_groups = (n + kApplyRows - 1) / kApplyRows;
   for (int64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {  // the same trip count in every wave of the block
-    const int64_t r = g * kSvdRows + wave;
+    const int64_t r = g * kApplyRows + wave;
     __syncthreads();
     yrow[wave][lane] = (r < n && lane < W) ? Y[r * kSvdLd + lane] : 0.0;
     __syncthreads();
@@ -255,8 +193,8 @@ extern "C" int hvae_svd_spmm(const int64_t* ptr, const int32_t* idx, const float
   HVAE_REQUIRE(svd_w_ok(W), "hvae_svd_spmm: W = %lld is not served (1 to %d)", (long long)W, HVAE_SVD_LD);
   HVAE_REQUIRE(ptr && idx && vals && X && out, "hvae_svd_spmm: null pointer");
   HVAE_REQUIRE(X != out, "hvae_svd_spmm: out may not alias X");
-  k_svd_spmm<<<(unsigned)cdiv(n_rows, kSvdRows), 256, 0, as_stream(stream)>>>(ptr, idx, vals, n_rows, n_cols, X, out,
-                                                                              (int)W);
+  k_svd_spmm<<<(unsigned)cdiv(n_rows, kGatherRows), 256, 0, as_stream(stream)>>>(ptr, idx, vals, n_rows, n_cols, X,
+                                                                                 out, (int)W);
   HVAE_LAUNCH_CHECK("k_svd_spmm");
   return HVAE_OK;
 }
@@ -299,7 +237,7 @@ extern "C" int hvae_svd_apply(const double* Y, int64_t n, int64_t W, const doubl
                (long long)W, (long long)W_out, HVAE_SVD_LD);
   HVAE_REQUIRE(Y && T && out, "hvae_svd_apply: null pointer");
   HVAE_REQUIRE(T != Y && T != out, "hvae_svd_apply: T may not alias Y or out");
-  const int64_t groups = cdiv(n, kSvdRows);
+  const int64_t groups = cdiv(n, kApplyRows);
   const unsigned grid = (unsigned)(groups < 1024 ? groups : 1024);
   k_svd_apply<<<grid, 256, 0, as_stream(stream)>>>(Y, n, (int)W, T, (int)W_out, out);
   HVAE_LAUNCH_CHECK("k_svd_apply");

@@ -5,7 +5,8 @@ reference's recommender API (fit / predict), evaluate_model (:411-471), run_all_
 (:536-544), and the same models/figures/baseline_results.json. SVD, Mult-VAE and LightGCN are separate trained
 models and are not run from here: asking for one is an error, never a silent skip. LightGCN is trained by
 src/ml/lightgcn.py (`make baseline-lightgcn`), SVD fitted by src/ml/svd.py (`make baseline-svd`) and Mult-VAE trained
-by src/ml/multvae.py (`make baseline-multvae`); all three reuse this module's evaluation and results file.
+by src/ml/multvae.py (`make baseline-multvae`); each constructs its model and hands it to this module's run_baseline:
+the data loading, timing, evaluation, table, results file and common flags are written once, below.
 
 The reference scores one test row at a time in a Python loop; here the rows are batched on the device. Scores
 come from libhvae (hvae_csc_col_stats for Popularity, the two-stage hvae_knn_* kernels for Item-KNN), the
@@ -279,43 +280,52 @@ def _select_models(models) -> list[str]:
     return names
 
 
-def save_results(all_results: dict, data_dir: str) -> Path:
-    """<data>/../models/figures/baseline_results.json in the reference's layout (baseline.py:522-531)."""
-    figures_path = Path(data_dir).parent / "models" / "figures"
-    figures_path.mkdir(parents=True, exist_ok=True)
-    out = figures_path / "baseline_results.json"
-    with open(out, "w") as f:
-        json.dump({m: {str(k): v for k, v in metrics.items()} for m, metrics in all_results.items()}, f, indent=2)
-    return out
+# =============================================================================
+# The runner (reference: baseline.py:474-544): every baseline command goes through these
+# =============================================================================
 
 
-def run_all_baselines(data_dir: str, k_values: list[int] | None = None, n_negatives: int | None = 99,
-                      models: list[str] | None = None) -> dict:
-    """Run the baselines one after the other on one numpy stream (reference: baseline.py:474-533)."""
-    k_values = k_values or [5, 10, 20]
-    names = _select_models(models)
-
+def load_eval_data(data_dir: str) -> tuple[csr_matrix, pd.DataFrame, dict, dict]:
+    """What an evaluation reads from a data directory: (the train + val input matrix, the test frame, user_to_idx,
+    item_to_idx)."""
     full_matrix, train_df, val_df, mappings = load_training_data(data_dir)
     user_to_idx, item_to_idx = mappings["user_to_idx"], mappings["item_to_idx"]
     input_matrix, _ = _build_input_matrix(train_df, val_df, user_to_idx, item_to_idx, full_matrix.shape)
-    test_df = pd.read_csv(Path(data_dir) / "test.csv")
+    return input_matrix, pd.read_csv(Path(data_dir) / "test.csv"), user_to_idx, item_to_idx
 
-    all_results = {}
-    for name in names:
-        model = BASELINES[name]()
-        logger.info(f"\n{'=' * 60}\nTraining {name}\n{'=' * 60}")
-        start_time = time.time()
-        model.fit(input_matrix)
-        if model.device is not None:
-            torch.cuda.synchronize(model.device)
-        training_time = round(time.time() - start_time, 2)
-        logger.info(f"{name} training time: {training_time:.1f}s")
-        results = evaluate_model(model, name, input_matrix, test_df, user_to_idx, item_to_idx, k_values, n_negatives)
-        results["training_time_seconds"] = training_time
-        all_results[name] = results
 
-    protocol = f"negative sampling ({n_negatives})" if n_negatives else "full ranking"
-    logger.info(f"\n{'=' * 70}\nBASELINE COMPARISON ({protocol})\n{'=' * 70}")
+def fit_and_evaluate(model: BaseRecommender, name: str, data: tuple, k_values: list[int],
+                     n_negatives: int | None) -> dict:
+    """Fit a constructed model on load_eval_data's matrix (timed to the end of its device work), evaluate it, and
+    return evaluate_model's results with training_time_seconds added."""
+    input_matrix, test_df, user_to_idx, item_to_idx = data
+    logger.info(f"\n{'=' * 60}\nTraining {name}\n{'=' * 60}")
+    start_time = time.time()
+    model.fit(input_matrix)
+    if model.device is not None:
+        torch.cuda.synchronize(model.device)
+    training_time = round(time.time() - start_time, 2)
+    logger.info(f"{name} training time: {training_time:.1f}s")
+    results = evaluate_model(model, name, input_matrix, test_df, user_to_idx, item_to_idx, k_values, n_negatives)
+    results["training_time_seconds"] = training_time
+    return results
+
+
+def write_results(all_results: dict, data_dir: str, keep_existing: bool) -> Path:
+    """Set the entries of all_results in <data>/../models/figures/baseline_results.json, the reference's layout
+    (baseline.py:522-531). With keep_existing the file's other entries stay, in their order (a one-model command
+    beside `make baseline`'s entries); without it the file is replaced, as the reference does."""
+    figures_path = Path(data_dir).parent / "models" / "figures"
+    figures_path.mkdir(parents=True, exist_ok=True)
+    out = figures_path / "baseline_results.json"
+    merged = json.loads(out.read_text()) if keep_existing and out.exists() else {}
+    merged.update({m: {str(k): v for k, v in metrics.items()} for m, metrics in all_results.items()})
+    with open(out, "w") as f:
+        json.dump(merged, f, indent=2)
+    return out
+
+
+def print_table(all_results: dict, k_values: list[int]) -> None:
     cols = [(f"Recall@{k}", k, "recall") for k in k_values] + [(f"NDCG@{k}", k, "ndcg") for k in k_values]
     width = 15 + 13 * len(cols)
     print(f"\n{'-' * width}\n{'Model':<15}" + "".join(f" | {c[0]:>10}" for c in cols) + f"\n{'-' * width}")
@@ -323,21 +333,52 @@ def run_all_baselines(data_dir: str, k_values: list[int] | None = None, n_negati
         print(f"{name:<15}" + "".join(f" | {metrics[k][m]:>10.4f}" for _, k, m in cols))
     print("-" * width)
 
-    logger.info(f"Saved to {save_results(all_results, data_dir)}")
+
+def run_baseline(model: BaseRecommender, name: str, data_dir: str, k_values: list[int] | None,
+                 n_negatives: int | None) -> dict:
+    """Fit and evaluate one constructed model as run_all_baselines does, and set its entry of the results file
+    beside the others."""
+    k_values = k_values or [5, 10, 20]
+    results = fit_and_evaluate(model, name, load_eval_data(data_dir), k_values, n_negatives)
+    print_table({name: results}, k_values)
+    logger.info(f"Saved to {write_results({name: results}, data_dir, keep_existing=True)}")
+    return results
+
+
+def run_all_baselines(data_dir: str, k_values: list[int] | None = None, n_negatives: int | None = 99,
+                      models: list[str] | None = None) -> dict:
+    """Run the baselines one after the other on one numpy stream (reference: baseline.py:474-533)."""
+    k_values = k_values or [5, 10, 20]
+    names = _select_models(models)
+    data = load_eval_data(data_dir)
+    all_results = {name: fit_and_evaluate(BASELINES[name](), name, data, k_values, n_negatives) for name in names}
+
+    protocol = f"negative sampling ({n_negatives})" if n_negatives else "full ranking"
+    logger.info(f"\n{'=' * 70}\nBASELINE COMPARISON ({protocol})\n{'=' * 70}")
+    print_table(all_results, k_values)
+    logger.info(f"Saved to {write_results(all_results, data_dir, keep_existing=False)}")
     return all_results
 
 
-def main() -> None:
-    parser = argparse.ArgumentParser(description="Evaluate the training-free baselines (MI355X)")
+def parse_args(description: str, add_flags=None) -> argparse.Namespace:
+    """The command line every baseline command shares (reference: baseline.py:536-544) plus the flags add_flags(parser)
+    adds; --n-negatives 0 (full ranking) comes back as None."""
+    parser = argparse.ArgumentParser(description=description)
     parser.add_argument("--data", default=str(config.DATA_DIR))
     parser.add_argument("--n-negatives", type=int, default=99, help="0 for full ranking")
     parser.add_argument("--k-values", type=int, nargs="+", default=[5, 10, 20])
-    parser.add_argument("--models", nargs="+", default=list(SERVED_MODELS),
-                        help="baselines to run, in order (served: Popularity, Item-KNN)")
+    if add_flags is not None:
+        add_flags(parser)
     args = parser.parse_args()
+    args.n_negatives = args.n_negatives if args.n_negatives > 0 else None
+    return args
 
-    n_negatives = args.n_negatives if args.n_negatives > 0 else None
-    run_all_baselines(args.data, args.k_values, n_negatives, models=args.models)
+
+def main() -> None:
+    args = parse_args("Evaluate the training-free baselines (MI355X)", lambda p: p.add_argument(
+        "--models", nargs="+", default=list(SERVED_MODELS),
+        help="baselines to run, in order (served: Popularity, Item-KNN)"))
+    run_all_baselines(args.data, args.k_values, args.n_negatives, models=args.models)
 
 
 if __name__ == "__main__":

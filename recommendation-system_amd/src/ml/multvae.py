@@ -21,22 +21,15 @@ unchanged; main() sets the "Mult-VAE" entry of models/figures/baseline_results.j
 """
 from __future__ import annotations
 
-import argparse
-import json
 import logging
-import time
-from pathlib import Path
 
 import numpy as np
-import pandas as pd
 import torch
 from scipy.sparse import csr_matrix
 
 from hvae import _lib, ops
 
-from ..config import config
-from .baseline import BaseRecommender, _build_input_matrix, _resolve_device, evaluate_model
-from .train import load_training_data
+from .baseline import BaseRecommender, _resolve_device, parse_args, run_baseline
 
 logger = logging.getLogger(__name__)
 
@@ -297,57 +290,21 @@ class MultVAERecommender(BaseRecommender):
         return ops.gemm(self.steps.hidden(users), P["Wd2"].t(), epi=TrainSteps._bias(P["bd2"]))
 
 
-def merge_results(results: dict, data_dir: str) -> Path:
-    """Set the "Mult-VAE" entry of <data>/../models/figures/baseline_results.json (baseline.save_results' file and
-    layout), keeping the other entries of an existing file."""
-    figures_path = Path(data_dir).parent / "models" / "figures"
-    figures_path.mkdir(parents=True, exist_ok=True)
-    out = figures_path / "baseline_results.json"
-    merged = json.loads(out.read_text()) if out.exists() else {}
-    merged[NAME] = {str(k): v for k, v in results.items()}
-    with open(out, "w") as f:
-        json.dump(merged, f, indent=2)
-    return out
-
-
 def run_multvae(data_dir: str, k_values: list[int] | None = None, n_negatives: int | None = 99, epochs: int = 50,
                 seed: int = 0, hidden_dim: int = 600, latent_dim: int = 200) -> dict:
     """Fit and evaluate Mult-VAE as the reference's run_all_baselines does for one model (baseline.py:474-533)."""
-    k_values = k_values or [5, 10, 20]
     model = MultVAERecommender(hidden_dim, latent_dim, epochs=epochs, seed=seed)
+    return run_baseline(model, NAME, data_dir, k_values, n_negatives)
 
-    full_matrix, train_df, val_df, mappings = load_training_data(data_dir)
-    user_to_idx, item_to_idx = mappings["user_to_idx"], mappings["item_to_idx"]
-    input_matrix, _ = _build_input_matrix(train_df, val_df, user_to_idx, item_to_idx, full_matrix.shape)
-    test_df = pd.read_csv(Path(data_dir) / "test.csv")
 
-    logger.info(f"\n{'=' * 60}\nTraining {NAME}\n{'=' * 60}")
-    start_time = time.time()
-    model.fit(input_matrix)
-    torch.cuda.synchronize(model.device)
-    training_time = round(time.time() - start_time, 2)
-    logger.info(f"{NAME} training time: {training_time:.1f}s")
-    results = evaluate_model(model, NAME, input_matrix, test_df, user_to_idx, item_to_idx, k_values, n_negatives)
-    results["training_time_seconds"] = training_time
-
-    cols = [(f"Recall@{k}", k, "recall") for k in k_values] + [(f"NDCG@{k}", k, "ndcg") for k in k_values]
-    print(f"{'Model':<15}" + "".join(f" | {c[0]:>10}" for c in cols))
-    print(f"{NAME:<15}" + "".join(f" | {results[k][m]:>10.4f}" for _, k, m in cols))
-    logger.info(f"Saved to {merge_results(results, data_dir)}")
-    return results
+def _add_flags(parser) -> None:
+    parser.add_argument("--epochs", type=int, default=50)
+    parser.add_argument("--seed", type=int, default=0, help="keys the device's dropout and eps streams")
 
 
 def main() -> None:
-    parser = argparse.ArgumentParser(description="Train and evaluate the Mult-VAE baseline (MI355X)")
-    parser.add_argument("--data", default=str(config.DATA_DIR))
-    parser.add_argument("--n-negatives", type=int, default=99, help="0 for full ranking")
-    parser.add_argument("--k-values", type=int, nargs="+", default=[5, 10, 20])
-    parser.add_argument("--epochs", type=int, default=50)
-    parser.add_argument("--seed", type=int, default=0, help="keys the device's dropout and eps streams")
-    args = parser.parse_args()
-
-    n_negatives = args.n_negatives if args.n_negatives > 0 else None
-    run_multvae(args.data, args.k_values, n_negatives, epochs=args.epochs, seed=args.seed)
+    args = parse_args("Train and evaluate the Mult-VAE baseline (MI355X)", _add_flags)
+    run_multvae(args.data, args.k_values, args.n_negatives, epochs=args.epochs, seed=args.seed)
 
 
 if __name__ == "__main__":

@@ -21,22 +21,15 @@ entry of models/figures/baseline_results.json beside the entries `make baseline`
 """
 from __future__ import annotations
 
-import argparse
-import json
 import logging
-import time
-from pathlib import Path
 
 import numpy as np
-import pandas as pd
 import torch
 from scipy.sparse import csr_matrix
 
 from hvae import ops
 
-from ..config import config
-from .baseline import BaseRecommender, _build_input_matrix, _resolve_device, evaluate_model
-from .train import load_training_data
+from .baseline import BaseRecommender, _resolve_device, parse_args, run_baseline
 
 logger = logging.getLogger(__name__)
 
@@ -163,56 +156,16 @@ class SVDRecommender(BaseRecommender):
         return ops.gemm(self._users32.index_select(0, rows), self._items32.t())
 
 
-def merge_results(results: dict, data_dir: str) -> Path:
-    """Set the "SVD" entry of <data>/../models/figures/baseline_results.json (baseline.save_results' file and
-    layout), keeping the other entries of an existing file."""
-    figures_path = Path(data_dir).parent / "models" / "figures"
-    figures_path.mkdir(parents=True, exist_ok=True)
-    out = figures_path / "baseline_results.json"
-    merged = json.loads(out.read_text()) if out.exists() else {}
-    merged[NAME] = {str(k): v for k, v in results.items()}
-    with open(out, "w") as f:
-        json.dump(merged, f, indent=2)
-    return out
-
-
 def run_svd(data_dir: str, k_values: list[int] | None = None, n_negatives: int | None = 99,
             n_components: int = 50) -> dict:
     """Fit and evaluate SVD as the reference's run_all_baselines does for one model (baseline.py:474-533)."""
-    k_values = k_values or [5, 10, 20]
-    model = SVDRecommender(n_components)
-
-    full_matrix, train_df, val_df, mappings = load_training_data(data_dir)
-    user_to_idx, item_to_idx = mappings["user_to_idx"], mappings["item_to_idx"]
-    input_matrix, _ = _build_input_matrix(train_df, val_df, user_to_idx, item_to_idx, full_matrix.shape)
-    test_df = pd.read_csv(Path(data_dir) / "test.csv")
-
-    logger.info(f"\n{'=' * 60}\nTraining {NAME}\n{'=' * 60}")
-    start_time = time.time()
-    model.fit(input_matrix)
-    torch.cuda.synchronize(model.device)
-    training_time = round(time.time() - start_time, 2)
-    logger.info(f"{NAME} training time: {training_time:.1f}s")
-    results = evaluate_model(model, NAME, input_matrix, test_df, user_to_idx, item_to_idx, k_values, n_negatives)
-    results["training_time_seconds"] = training_time
-
-    cols = [(f"Recall@{k}", k, "recall") for k in k_values] + [(f"NDCG@{k}", k, "ndcg") for k in k_values]
-    print(f"{'Model':<15}" + "".join(f" | {c[0]:>10}" for c in cols))
-    print(f"{NAME:<15}" + "".join(f" | {results[k][m]:>10.4f}" for _, k, m in cols))
-    logger.info(f"Saved to {merge_results(results, data_dir)}")
-    return results
+    return run_baseline(SVDRecommender(n_components), NAME, data_dir, k_values, n_negatives)
 
 
 def main() -> None:
-    parser = argparse.ArgumentParser(description="Fit and evaluate the SVD baseline (MI355X)")
-    parser.add_argument("--data", default=str(config.DATA_DIR))
-    parser.add_argument("--n-negatives", type=int, default=99, help="0 for full ranking")
-    parser.add_argument("--k-values", type=int, nargs="+", default=[5, 10, 20])
-    parser.add_argument("--n-components", type=int, default=50, help="served: 1 to 54")
-    args = parser.parse_args()
-
-    n_negatives = args.n_negatives if args.n_negatives > 0 else None
-    run_svd(args.data, args.k_values, n_negatives, n_components=args.n_components)
+    args = parse_args("Fit and evaluate the SVD baseline (MI355X)", lambda p: p.add_argument(
+        "--n-components", type=int, default=50, help="served: 1 to 54"))
+    run_svd(args.data, args.k_values, args.n_negatives, n_components=args.n_components)
 
 
 if __name__ == "__main__":

@@ -98,6 +98,40 @@ def test_results_json_layout(tmp_path, monkeypatch):
         assert set(res[name]) == {5, 10, "training_time_seconds"}
 
 
+@pytest.mark.parametrize("name", ["LightGCN", "SVD", "Mult-VAE"])
+def test_results_json_merge_keeps_other_entries(tmp_path, name):
+    """The one-model commands' mode of the shared writer: their entry set, a stale one replaced, the other entries
+    and the order of the existing keys kept."""
+    import src.ml.baseline as b
+    data = tmp_path / "data"
+    data.mkdir()
+    res = {5: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5}, "training_time_seconds": 1.25}
+    out = b.write_results({name: res}, str(data), keep_existing=True)  # no file yet
+    assert out == tmp_path / "models" / "figures" / "baseline_results.json"
+    assert json.loads(out.read_text()) == {name: {"5": res[5], "training_time_seconds": 1.25}}
+    pop = {"5": {"recall": 0.1, "ndcg": 0.1, "hit_ratio": 0.1}, "training_time_seconds": 0.01}
+    out.write_text(json.dumps({"Popularity": pop, name: {"stale": 1}, "Item-KNN": pop}))
+    b.write_results({name: res}, str(data), keep_existing=True)
+    got = json.loads(out.read_text())
+    assert list(got) == ["Popularity", name, "Item-KNN"] and got["Popularity"] == pop and got["Item-KNN"] == pop
+    assert got[name] == {"5": res[5], "training_time_seconds": 1.25}
+
+
+def test_results_json_replace_drops_other_entries(tmp_path):
+    """run_all_baselines' mode of the shared writer: the file is replaced, as the reference does."""
+    import src.ml.baseline as b
+    data = tmp_path / "data"
+    data.mkdir()
+    res = {5: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5}, "training_time_seconds": 1.25}
+    out = tmp_path / "models" / "figures" / "baseline_results.json"
+    out.parent.mkdir(parents=True)
+    out.write_text(json.dumps({"SVD": {"stale": 1}, "Popularity": {"stale": 1}}))
+    assert b.write_results({"Item-KNN": res, "Popularity": res}, str(data), keep_existing=False) == out
+    want = {"5": res[5], "training_time_seconds": 1.25}
+    got = json.loads(out.read_text())
+    assert list(got) == ["Item-KNN", "Popularity"] and got == {"Item-KNN": want, "Popularity": want}
+
+
 def test_build_input_matrix_sums_duplicates_and_filters_positives():
     import pandas as pd
     import src.ml.baseline as b

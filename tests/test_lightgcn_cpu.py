@@ -1,6 +1,6 @@
 """`make baseline-lightgcn` without a GPU: the fixture's own consistency, the host half of LightGCNRecommender.fit
 (the init draws, the epoch stream and its summation plan) against the reference's recorded draws, the command
-line, both Makefile targets, the refused shapes and the results-file merge."""
+line, both Makefile targets, the refused shapes and run_lightgcn through the shared runner."""
 import argparse
 import json
 import subprocess
@@ -179,24 +179,9 @@ def test_cli_refuses_an_unserved_dim_before_reading_data(tmp_path):
             lg.main()
 
 
-def test_results_json_merge_keeps_other_entries(tmp_path):
-    import src.ml.lightgcn as lg
-    data = tmp_path / "data"
-    data.mkdir()
-    res = {5: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5}, "training_time_seconds": 1.25}
-    out = lg.merge_results(res, str(data))  # no file yet
-    assert out == tmp_path / "models" / "figures" / "baseline_results.json"
-    assert json.loads(out.read_text()) == {"LightGCN": {"5": res[5], "training_time_seconds": 1.25}}
-    pop = {"5": {"recall": 0.1, "ndcg": 0.1, "hit_ratio": 0.1}, "training_time_seconds": 0.01}
-    out.write_text(json.dumps({"Popularity": pop, "LightGCN": {"stale": 1}}))
-    lg.merge_results(res, str(data))
-    got = json.loads(out.read_text())
-    assert list(got) == ["Popularity", "LightGCN"] and got["Popularity"] == pop
-    assert got["LightGCN"] == {"5": res[5], "training_time_seconds": 1.25}
-
-
 def test_run_lightgcn_fits_evaluates_and_merges(tmp_path, monkeypatch):
     """run_lightgcn with the device work stubbed out: the train + val matrix, the test frame, the timing entry."""
+    import src.ml.baseline as b
     import src.ml.lightgcn as lg
     from gen import write_planted_artifacts
     data, _ = write_planted_artifacts(tmp_path, dict(n_users=30, n_items=40, d=4, n_clusters=2))
@@ -211,8 +196,7 @@ def test_run_lightgcn_fits_evaluates_and_merges(tmp_path, monkeypatch):
         return {k: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5} for k in k_values}
 
     monkeypatch.setattr(lg.LightGCNRecommender, "fit", fake_fit)
-    monkeypatch.setattr(lg, "evaluate_model", fake_eval)
-    monkeypatch.setattr(lg.torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(b, "evaluate_model", fake_eval)
     res = lg.run_lightgcn(str(data), [5, 10], None, embedding_dim=128, n_layers=2, epochs=3)
     assert calls == [("fit", (30, 40), 128, 2, 3), ("LightGCN", (30, 40), 30, (5, 10), None)]
     out = json.loads((tmp_path / "models" / "figures" / "baseline_results.json").read_text())

@@ -121,6 +121,32 @@ def test_cli_passes_its_arguments(argv, want):
     assert args == want[:3] and kw == want[3]
 
 
+def test_run_multvae_fits_evaluates_and_merges(tmp_path, monkeypatch):
+    """run_multvae with the device work stubbed out: the train + val matrix, the test frame, the timing entry."""
+    import json
+    import src.ml.baseline as b
+    import src.ml.multvae as mv
+    from gen import write_planted_artifacts
+    data, _ = write_planted_artifacts(tmp_path, dict(n_users=30, n_items=40, d=4, n_clusters=2))
+    calls = []
+
+    def fake_fit(self, m):
+        self.device = None
+        calls.append(("fit", m.shape, self.hidden_dim, self.latent_dim, self.epochs, self.seed))
+
+    def fake_eval(model, name, matrix, test_df, u2i, i2i, k_values, n_negatives):
+        calls.append((name, matrix.shape, len(test_df), tuple(k_values), n_negatives))
+        return {k: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5} for k in k_values}
+
+    monkeypatch.setattr(mv.MultVAERecommender, "fit", fake_fit)
+    monkeypatch.setattr(b, "evaluate_model", fake_eval)
+    res = mv.run_multvae(str(data), [5, 10], None, epochs=3, seed=9, hidden_dim=64, latent_dim=16)
+    assert calls == [("fit", (30, 40), 64, 16, 3, 9), ("Mult-VAE", (30, 40), 30, (5, 10), None)]
+    out = json.loads((tmp_path / "models" / "figures" / "baseline_results.json").read_text())
+    assert list(out) == ["Mult-VAE"] and list(out["Mult-VAE"]) == ["5", "10", "training_time_seconds"]
+    assert isinstance(out["Mult-VAE"]["training_time_seconds"], float) and set(res) == {5, 10, "training_time_seconds"}
+
+
 @pytest.mark.parametrize("target,n_neg", [("baseline-multvae", "99"), ("baseline-multvae-full", "0")])
 def test_makefile_targets(target, n_neg):
     r = subprocess.run(["make", "-n", "-C", str(PKG), target, "PYTHON=python", "DATA_DIR=data"], capture_output=True,

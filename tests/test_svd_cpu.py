@@ -1,6 +1,6 @@
 """`make baseline-svd` without a GPU: the fixture's own consistency and the float64 restatement of the device
 algorithm against it, the host half of SVDRecommender.fit (the sketch, the eigen step), the command line, both
-Makefile targets, the refused shapes, the results-file merge and the ABI."""
+Makefile targets, the refused shapes, run_svd through the shared runner and the ABI."""
 import argparse
 import json
 import subprocess
@@ -249,25 +249,10 @@ def test_fit_refuses_a_matrix_smaller_than_the_sketch_before_any_device_work(mon
         svd.SVDRecommender(n_components=50).fit(csr_matrix(np.ones((59, 200))))
 
 
-# ------------------------------------------------------------------------------------------- the results file ----
-def test_results_json_merge_keeps_other_entries(tmp_path):
-    import src.ml.svd as svd
-    data = tmp_path / "data"
-    data.mkdir()
-    res = {5: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5}, "training_time_seconds": 1.25}
-    out = svd.merge_results(res, str(data))  # no file yet
-    assert out == tmp_path / "models" / "figures" / "baseline_results.json"
-    assert json.loads(out.read_text()) == {"SVD": {"5": res[5], "training_time_seconds": 1.25}}
-    pop = {"5": {"recall": 0.1, "ndcg": 0.1, "hit_ratio": 0.1}, "training_time_seconds": 0.01}
-    out.write_text(json.dumps({"Popularity": pop, "SVD": {"stale": 1}, "LightGCN": pop}))
-    svd.merge_results(res, str(data))
-    got = json.loads(out.read_text())
-    assert list(got) == ["Popularity", "SVD", "LightGCN"] and got["Popularity"] == pop and got["LightGCN"] == pop
-    assert got["SVD"] == {"5": res[5], "training_time_seconds": 1.25}
-
-
+# ------------------------------------------------------------------------------------------------- the runner ----
 def test_run_svd_fits_evaluates_and_merges(tmp_path, monkeypatch):
     """run_svd with the device work stubbed out: the train + val matrix, the test frame, the timing entry."""
+    import src.ml.baseline as b
     import src.ml.svd as svd
     from gen import write_planted_artifacts
     data, _ = write_planted_artifacts(tmp_path, dict(n_users=30, n_items=40, d=4, n_clusters=2))
@@ -282,8 +267,7 @@ def test_run_svd_fits_evaluates_and_merges(tmp_path, monkeypatch):
         return {k: {"recall": 0.5, "ndcg": 0.25, "hit_ratio": 0.5} for k in k_values}
 
     monkeypatch.setattr(svd.SVDRecommender, "fit", fake_fit)
-    monkeypatch.setattr(svd, "evaluate_model", fake_eval)
-    monkeypatch.setattr(svd.torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(b, "evaluate_model", fake_eval)
     res = svd.run_svd(str(data), [5, 10], None, n_components=8)
     assert calls == [("fit", (30, 40), 8), ("SVD", (30, 40), 30, (5, 10), None)]
     out = json.loads((tmp_path / "models" / "figures" / "baseline_results.json").read_text())
