@@ -921,6 +921,41 @@ int hvae_tsne_update(const double* attr, const double* rep, const double* z, int
                      const int64_t* ptr, const int32_t* col, const double* pval, int want_stats, double* stats,
                      double* grad_out, double* z_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------- SBERT item encoder (K22) -- */
+/* The item-text encoder (ItemEmbeddingGenerator, src/preprocessing/embeddings.py:27-131: SentenceTransformer.encode
+ * with normalize_embeddings=True) for a BERT-family model: post-LayerNorm BertModel -> mean pooling -> L2
+ * normalisation, all fp32. The sequences of a pass are packed without padding: cu (int32 [S + 1], cu[0] = 0,
+ * ascending) holds the token offsets, T = cu[S] token rows, row t of sequence s has position t - cu[s]. There is no
+ * attention mask. Every linear layer is hvae_gemm_f32 (QKV against the concatenated query | key | value weights,
+ * attention output and FFN down with HVAE_EPI_BIAS, FFN up with HVAE_EPI_BIAS_GELU_DROP and train = 0); these entry
+ * points are what lies between. No atomics; every sum has one fixed order that depends on the shapes only
+ * (csrc/hvae_sbert.hip states each), so two runs give the same bits. The caller owns every buffer and the stream;
+ * nothing here allocates or waits. Float arrays are 16-byte aligned; H is a multiple of 4 in 4 .. 1024;
+ * 3 H T < 2^31. Indices read from device memory are checked on the device: a bad one gives a NaN row or an
+ * untouched output, never an access out of bounds (the host wrappers of hvae/ops.py refuse them beforehand).
+ *
+ * hvae_sbert_supported: host arithmetic; 1 where heads divides H, H / heads is 32 or 64, H % 4 == 0, H <= 1024 and
+ * 1 <= max_len <= 512.
+ * hvae_sbert_embed_ln: out[t] = LayerNorm(word[ids[t]] + pos[t - cu[s]] + type0; ln_w, ln_b, eps), [T, H]. word is
+ * [vocab, H], pos [max_pos, H], type0 [H] (token type 0's row). One wave per row.
+ * hvae_sbert_add_ln: out = LayerNorm(x + res; ln_w, ln_b, eps) per row of [T, H]; out may be x or res.
+ * hvae_sbert_attention: qkv [T, 3 H] -> ctx [T, H], ctx = softmax(Q K^T / sqrt(dh)) V inside each sequence and head
+ * (dh = H / heads in {32, 64}, sequences of 1 .. 512 tokens), a streaming softmax on v_mfma_f32_16x16x4_f32. work is
+ * int32 [n_work, 2]: the (sequence, 64-query chunk) pairs to compute, every chunk of every sequence once; one launch
+ * of n_work x heads blocks. Rows of ctx that no work item names stay untouched; ctx may not alias qkv.
+ * hvae_sbert_pool_norm: out[s] = mean of x's rows cu[s] .. cu[s + 1] - 1, divided by max(its L2 norm, 1e-12), [S, H].
+ */
+int hvae_sbert_supported(int64_t H, int64_t heads, int64_t max_len);
+int hvae_sbert_embed_ln(const int32_t* ids, const int32_t* cu, int64_t S, int64_t T, const float* word, int64_t vocab,
+                        const float* pos, int64_t max_pos, const float* type0, const float* ln_w, const float* ln_b,
+                        float eps, int64_t H, float* out, void* stream);
+int hvae_sbert_add_ln(const float* x, const float* res, const float* ln_w, const float* ln_b, float eps, int64_t T,
+                      int64_t H, float* out, void* stream);
+int hvae_sbert_attention(const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H, int64_t heads,
+                         const int32_t* work, int64_t n_work, float* ctx, void* stream);
+int hvae_sbert_pool_norm(const float* x, const int32_t* cu, int64_t S, int64_t T, int64_t H, float* out,
+                         void* stream);
+
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and
  * released by hvae_host_csr_free. */

@@ -250,6 +250,11 @@ SIGNATURES = {
     "hvae_tsne_update_workspace": (sz, [i64]),
     "hvae_tsne_update": (cint, [vp, vp, vp, i64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, cint, vp, vp, vp, vp, sz,
                                 vp]),
+    "hvae_sbert_supported": (cint, [i64, i64, i64]),
+    "hvae_sbert_embed_ln": (cint, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, f32, i64, vp, vp]),
+    "hvae_sbert_add_ln": (cint, [vp, vp, vp, vp, f32, i64, i64, vp, vp]),
+    "hvae_sbert_attention": (cint, [vp, vp, i64, i64, i64, i64, vp, i64, vp, vp]),
+    "hvae_sbert_pool_norm": (cint, [vp, vp, i64, i64, i64, vp, vp]),
     "hvae_mvae_encoder_fwd": (cint, [P(CsrBatch), vp, vp, i64, f32, f32, vp, vp, u64, vp, cint, vp, vp, vp, vp]),
     "hvae_mvae_tanh_drop_fwd": (cint, [vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, vp, i64, vp]),
     "hvae_mvae_tanh_drop_bwd": (cint, [vp, i64, vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, i64, vp]),

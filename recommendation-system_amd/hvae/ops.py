@@ -1150,3 +1150,138 @@ def tsne_update(attr, rep, z, gains, upd, y_in, y_out, exaggeration: float, mome
                                  ptr(grad_out), ptr(z_out), ptr(ws), ws.numel() if want else 0, stream_of(y_in)),
           "hvae_tsne_update")
     return y_out
+
+
+# -------------------------------------------------------------------- SBERT --
+SBERT_MAX_LEN, SBERT_MAX_H, SBERT_CHUNK = 512, 1024, 64  # csrc/hvae_sbert.hip kSbMaxLen, kSbMaxH, kSbQB
+SBERT_SERVED = (f"served: head width 32 or 64, H a multiple of 4 up to {SBERT_MAX_H}, sequences of 1 to "
+                f"{SBERT_MAX_LEN} tokens")
+
+
+def sbert_supported(H: int, heads: int, max_len: int) -> bool:
+    return bool(lib().hvae_sbert_supported(int(H), int(heads), int(max_len)))
+
+
+class SbertPack:
+    """The packed sequences of one pass: ids int32 [T], cu int32 [S + 1] and the attention's work list int32
+    [n_work, 2] of (sequence, 64-query chunk) pairs, on the device. Built from host arrays, so that what the device
+    cannot report is refused here: an id below 0 (the upper bound is checked against the table in sbert_embed_ln), an
+    empty sequence or a non-monotone cu, a sequence of more than 512 tokens."""
+
+    def __init__(self, ids, cu, device):
+        import numpy as np
+        ids = np.ascontiguousarray(ids)
+        cu = np.ascontiguousarray(cu)
+        if ids.ndim != 1 or cu.ndim != 1 or cu.size < 2 or ids.dtype.kind not in "iu" or cu.dtype.kind not in "iu":
+            raise ValueError("SbertPack: ids [T] and cu [S + 1] must be integer vectors")
+        ids, cu = ids.astype(np.int64), cu.astype(np.int64)
+        if cu[0] != 0 or cu[-1] != ids.size or (np.diff(cu) < 1).any():
+            raise ValueError(f"SbertPack: cu must start at 0, end at T = {ids.size} and increase strictly "
+                             f"(no empty sequence); got cu[0] = {cu[0]}, cu[-1] = {cu[-1]}, smallest step "
+                             f"{int(np.diff(cu).min())}")
+        lens = np.diff(cu)
+        if lens.max() > SBERT_MAX_LEN:
+            raise ValueError(f"SbertPack: a sequence of {int(lens.max())} tokens is not served; {SBERT_SERVED}")
+        if ids.size and ids.min() < 0:
+            raise ValueError(f"SbertPack: token id {int(ids.min())} is outside [0, vocab)")
+        self.S, self.T = int(cu.size - 1), int(ids.size)
+        self.max_len, self.id_max = int(lens.max()), int(ids.max())
+        chunks = (lens + SBERT_CHUNK - 1) // SBERT_CHUNK
+        seq = np.repeat(np.arange(self.S), chunks)
+        first = np.repeat(np.cumsum(chunks) - chunks, chunks)
+        work = np.stack([seq, np.arange(seq.size) - first], axis=1).astype(np.int32)
+        self.n_work = int(work.shape[0])
+        self.ids = torch.as_tensor(ids.astype(np.int32), device=device)
+        self.cu = torch.as_tensor(cu.astype(np.int32), device=device)
+        self.work = torch.as_tensor(work, device=device)
+        require_hip(self.ids)
+
+
+def _sbert_mat(what: str, name: str, t: torch.Tensor, rows: int, cols: int):
+    require_hip(t)
+    if t.dtype != torch.float32 or tuple(t.shape) != (rows, cols) or not t.is_contiguous() or t.data_ptr() % 16:
+        raise ValueError(f"{what}: {name} must be a contiguous, 16-byte aligned float32 [{rows}, {cols}] matrix, got "
+                         f"{tuple(t.shape)} {t.dtype} with strides {tuple(t.stride())}")
+
+
+def _sbert_width(what: str, H: int, T: int) -> None:
+    if H < 4 or H > SBERT_MAX_H or H % 4:
+        raise ValueError(f"{what}: H = {H} is not served; {SBERT_SERVED}")
+    if 3 * H * T >= 2 ** 31:
+        raise ValueError(f"{what}: T = {T} rows of width {H} in one pass is not served (3 H T < 2^31)")
+
+
+def sbert_embed_ln(pack: SbertPack, word, pos, type0, ln_w, ln_b, eps: float, out=None):
+    """out[t] = LayerNorm(word[ids[t]] + pos[t - cu[s]] + type0) over the packed rows (hvae_sbert_embed_ln)."""
+    what = "sbert_embed_ln"
+    if word.dim() != 2 or pos.dim() != 2:
+        raise ValueError(f"{what}: word [vocab, H] and pos [max_pos, H] must be matrices")
+    vocab, H = word.shape
+    _sbert_width(what, H, pack.T)
+    _sbert_mat(what, "word", word, vocab, H)
+    _sbert_mat(what, "pos", pos, pos.shape[0], H)
+    for name, v in (("type0", type0), ("ln_w", ln_w), ("ln_b", ln_b)):
+        _sbert_mat(what, name, v.view(1, -1), 1, H)
+    if pack.id_max >= vocab:
+        raise ValueError(f"{what}: token id {pack.id_max} is outside [0, vocab = {vocab})")
+    if pack.max_len > pos.shape[0]:
+        raise ValueError(f"{what}: a sequence of {pack.max_len} tokens is longer than the position table "
+                         f"({pos.shape[0]} rows)")
+    out = torch.empty(pack.T, H, device=word.device) if out is None else out
+    _sbert_mat(what, "out", out, pack.T, H)
+    check(lib().hvae_sbert_embed_ln(ptr(pack.ids), ptr(pack.cu), pack.S, pack.T, ptr(word), vocab, ptr(pos),
+                                    pos.shape[0], ptr(type0), ptr(ln_w), ptr(ln_b), float(eps), H, ptr(out),
+                                    stream_of(word)), "hvae_sbert_embed_ln")
+    return out
+
+
+def sbert_add_ln(x, res, ln_w, ln_b, eps: float, out=None):
+    """out = LayerNorm(x + res) per row (hvae_sbert_add_ln); out may be x or res."""
+    what = "sbert_add_ln"
+    if x.dim() != 2:
+        raise ValueError(f"{what}: x must be a float32 [T, H] matrix")
+    T, H = x.shape
+    _sbert_width(what, H, T)
+    out = torch.empty_like(x) if out is None else out
+    for name, t in (("x", x), ("res", res), ("out", out)):
+        _sbert_mat(what, name, t, T, H)
+    for name, v in (("ln_w", ln_w), ("ln_b", ln_b)):
+        _sbert_mat(what, name, v.view(1, -1), 1, H)
+    check(lib().hvae_sbert_add_ln(ptr(x), ptr(res), ptr(ln_w), ptr(ln_b), float(eps), T, H, ptr(out), stream_of(x)),
+          "hvae_sbert_add_ln")
+    return out
+
+
+def sbert_attention(qkv, pack: SbertPack, heads: int, ctx=None):
+    """ctx [T, H] = softmax(Q K^T / sqrt(dh)) V inside each sequence and head, from qkv [T, 3 H]
+    (hvae_sbert_attention). ctx may have more than T rows: rows from T on are not touched."""
+    what = "sbert_attention"
+    if qkv.dim() != 2 or qkv.shape[1] % 3:
+        raise ValueError(f"{what}: qkv must be a float32 [T, 3 H] matrix, got {tuple(qkv.shape)}")
+    H = qkv.shape[1] // 3
+    if not sbert_supported(H, heads, pack.max_len):
+        raise ValueError(f"{what}: H = {H} with {heads} heads and {pack.max_len} tokens is not served; {SBERT_SERVED}")
+    _sbert_width(what, H, pack.T)
+    _sbert_mat(what, "qkv", qkv, pack.T, 3 * H)
+    ctx = torch.empty(pack.T, H, device=qkv.device) if ctx is None else ctx
+    if ctx.dim() != 2 or ctx.shape[0] < pack.T:
+        raise ValueError(f"{what}: ctx needs at least {pack.T} rows")
+    _sbert_mat(what, "ctx", ctx, ctx.shape[0], H)
+    check(lib().hvae_sbert_attention(ptr(qkv), ptr(pack.cu), pack.S, pack.T, H, int(heads), ptr(pack.work),
+                                     pack.n_work, ptr(ctx), stream_of(qkv)), "hvae_sbert_attention")
+    return ctx
+
+
+def sbert_pool_norm(x, pack: SbertPack, out=None):
+    """out[s] = the mean of sequence s's rows of x, divided by max(its L2 norm, 1e-12) (hvae_sbert_pool_norm)."""
+    what = "sbert_pool_norm"
+    if x.dim() != 2:
+        raise ValueError(f"{what}: x must be a float32 [T, H] matrix")
+    H = x.shape[1]
+    _sbert_width(what, H, pack.T)
+    _sbert_mat(what, "x", x, pack.T, H)
+    out = torch.empty(pack.S, H, device=x.device) if out is None else out
+    _sbert_mat(what, "out", out, pack.S, H)
+    check(lib().hvae_sbert_pool_norm(ptr(x), ptr(pack.cu), pack.S, pack.T, H, ptr(out), stream_of(x)),
+          "hvae_sbert_pool_norm")
+    return out

@@ -23,6 +23,8 @@ class Config:
     MODEL_FILE = os.getenv("MODEL_FILE", str(MODEL_DIR / "best_model.pth"))
     ENCODER_FILE = os.getenv("ENCODER_FILE", str(MODEL_DIR / "label_encoders.pkl"))
     EMBEDDINGS_FILE = os.getenv("EMBEDDINGS_FILE", str(EMBEDDINGS_DIR / "item_embeddings.npy"))
+    # where src.preprocessing.embeddings looks a model name up: <SBERT_MODEL_DIR>/<name>; nothing is ever fetched
+    SBERT_MODEL_DIR = os.getenv("SBERT_MODEL_DIR", str(MODEL_DIR / "sbert"))
 
     BATCH_SIZE = int(os.getenv("BATCH_SIZE", 64))
     LEARNING_RATE = float(os.getenv("LEARNING_RATE", 1e-3))
