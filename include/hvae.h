@@ -699,6 +699,16 @@ int hvae_topk_fused_plan(int64_t R, int64_t N, int64_t D, int64_t K, hvae_topk_p
 int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_ptr, int64_t n_users,
                           const int32_t* col_idx, int64_t n_items, const int32_t* users, const int32_t* tests, int64_t n_rows,
                           int32_t n_neg, int32_t* out, int32_t* counts);
+/* The same sampler with a draw count per row, for DatasetBuilder.create_negative_samples
+ * (src/preprocessing/dataset.py:93-135): row r draws np.random.choice(available, n_draw[r], replace=False) into
+ * out[out_ptr[r] .. out_ptr[r] + n_draw[r]) and counts[r] = n_draw[r]. tests may be NULL: then nothing but the
+ * user's CSR row is excluded. n_draw[r] <= 32767. A row with fewer available items than draws is numpy's
+ * replace=True path, which calls another generator: HVAE_ERR_UNSUPPORTED before anything is drawn, the state
+ * untouched. */
+int hvae_negatives_legacy_rows(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_ptr, int64_t n_users,
+                               const int32_t* col_idx, int64_t n_items, const int32_t* users, const int32_t* tests,
+                               const int32_t* n_draw, const int64_t* out_ptr, int64_t n_rows, int32_t* out,
+                               int32_t* counts);
 
 /* ------------------------------------------------------- baselines (K17) -- */
 /* The training-free baselines of src/ml/baseline.py over the train+val matrix M [n_users, n_items]. The kernels
@@ -955,6 +965,50 @@ int hvae_sbert_attention(const float* qkv, const int32_t* cu, int64_t S, int64_t
                          const int32_t* work, int64_t n_work, float* ctx, void* stream);
 int hvae_sbert_pool_norm(const float* x, const int32_t* cu, int64_t S, int64_t T, int64_t H, float* out,
                          void* stream);
+
+/* ------------------------------------------------------ preprocessing (K23) -- */
+/* The index work of `make preprocess` (src/preprocessing/cleaning.py:86-117, src/preprocessing/dataset.py:37-91)
+ * over integer columns on the device. n records, 1 <= n <= 2^31 - 1; user and item codes are int32 in [0, n_users)
+ * and [0, n_items). Every output is an integer or an fp32 sum of the records' values in input order, so it is exact
+ * and bitwise reproducible; the only atomics are integer adds. The caller owns every buffer, the workspace (256-byte
+ * aligned, at least the matching *_workspace() bytes; a query returns 0 for sizes the call refuses) and the stream;
+ * nothing here allocates or waits. Scalars that the device computes (n_classes, n_alive, rounds, lens, nnz) stay on
+ * the device. A code out of range never indexes anything: its record is dead (kcore) or left out (csr).
+ *
+ * hvae_prep_encode: LabelEncoder.fit + transform for string ids. keys [n, W] row-major, W in 1 .. 4: each id's
+ * UTF-8 bytes, NUL-padded to 8 W bytes and packed by the host into big-endian 64-bit words, so that word order is
+ * byte order is Python's code-point order, which is the order of LabelEncoder.classes_. codes[i] = the rank of key i
+ * among the distinct keys; *n_classes = their number; first[c] (capacity n) = the smallest record index that carries
+ * class c, from which the host reads the class strings. W stable sort passes, least significant word first. */
+size_t hvae_prep_encode_workspace(int64_t n, int W);
+int hvae_prep_encode(const uint64_t* keys, int64_t n, int W, int32_t* codes, int32_t* n_classes, int32_t* first,
+                     void* ws, size_t ws_bytes, void* stream);
+/* hvae_prep_kcore: filter_by_interactions. A round histograms users over the live records and kills the records of
+ * users below min_user, then histograms items over what is left and kills the records of items below min_item. All
+ * max_iterations rounds are enqueued at once; a round that follows one that removed nothing returns at once, as the
+ * reference's loop ends there. alive [n] bytes (1 = kept), *n_alive = the live count, *rounds = the number of rounds
+ * that removed a record (the reference's loop runs one more, unless max_iterations cut it short). */
+size_t hvae_prep_kcore_workspace(int64_t n_users, int64_t n_items, int32_t max_iterations);
+int hvae_prep_kcore(const int32_t* ucode, const int32_t* icode, int64_t n, int64_t n_users, int64_t n_items,
+                    int32_t min_user, int32_t min_item, int32_t max_iterations, uint8_t* alive, int64_t* n_alive,
+                    int32_t* rounds, void* ws, size_t ws_bytes, void* stream);
+/* hvae_prep_split: leave_one_out_split. perm [n] = the record indices stably sorted by (user code, ts), ts a signed
+ * int64 (the host maps datetime64 and float64 to it in order, NaT and NaN to INT64_MAX). Of each user's run the
+ * last record goes to test when the run has 2 or more, the one before it to val when the run has 3 or more, the
+ * rest to train. train_idx / val_idx / test_idx (capacity n each) receive the record indices of each part in sorted
+ * order; lens [3] = their lengths (train, val, test). */
+size_t hvae_prep_split_workspace(int64_t n);
+int hvae_prep_split(const int32_t* ucode, const int64_t* ts, int64_t n, int64_t n_users, int32_t* perm,
+                    int32_t* train_idx, int32_t* val_idx, int32_t* test_idx, int64_t* lens, void* ws, size_t ws_bytes,
+                    void* stream);
+/* hvae_prep_csr: create_interaction_matrix, the canonical CSR of all records in hvae_host_csr's layout on the
+ * device: row_ptr int64 [n_users + 1], col_idx int32 and out_vals fp32 (capacity n each), columns ascending within
+ * a row, duplicate (user, item) pairs summed in input order, *nnz = the stored entries. An entry whose values sum to
+ * zero is stored like any other (the reference's matrix_density counts it). */
+size_t hvae_prep_csr_workspace(int64_t n, int64_t n_users);
+int hvae_prep_csr(const int32_t* ucode, const int32_t* icode, const float* vals, int64_t n, int64_t n_users,
+                  int64_t n_items, int64_t* row_ptr, int32_t* col_idx, float* out_vals, int64_t* nnz, void* ws,
+                  size_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------- data artifacts (host) -- */
 /* A host CSR plus the file's users, allocated by hvae_read_interactions and

@@ -232,13 +232,13 @@ void replay_row(int32_t A, int32_t n_neg, const int32_t* js, At* at, int32_t* sr
   for (int32_t q = 0; q < n_neg; ++q) at[src[q]] = -1;
 }
 
-// The ascending items neither in the user's training row nor the test item (np.where(mask)[0]); ex[] is all 0
-// on entry and on return. Returns their count.
+// The ascending items neither in the user's training row nor the test item (np.where(mask)[0]); t < 0: no test
+// item, only the row is excluded. ex[] is all 0 on entry and on return. Returns their count.
 int32_t available_row(const int64_t* row_ptr, const int32_t* col_idx, int64_t n_items, int32_t u, int32_t t,
                       uint8_t* ex, int32_t* avail) {
   const int64_t b = row_ptr[u], e = row_ptr[u + 1];
   for (int64_t k = b; k < e; ++k) ex[col_idx[k]] = 1;
-  ex[t] = 1;
+  if (t >= 0) ex[t] = 1;
   int32_t A = 0;
   if (avail) {
     for (int32_t i = 0; i < (int32_t)n_items; ++i) {
@@ -251,11 +251,11 @@ int32_t available_row(const int64_t* row_ptr, const int32_t* col_idx, int64_t n_
       x += ex[col_idx[k]];  // each distinct item once
       ex[col_idx[k]] = 0;
     }
-    x += ex[t];
+    if (t >= 0) x += ex[t];
     A = (int32_t)n_items - x;
   }
   for (int64_t k = b; k < e; ++k) ex[col_idx[k]] = 0;
-  ex[t] = 0;
+  if (t >= 0) ex[t] = 0;
   return A;
 }
 
@@ -275,20 +275,17 @@ bool use_avx512() {
 // the row's words are consumed, then the stream advanced past them (the count-only draw: no stores). Up to
 // kWorkers threads meanwhile finish chunk c - 1, each row independently: regenerate the row's words from its
 // snapshot (the stored draw), list the available items and replay the swaps.
-extern "C" int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_ptr,
-                                     int64_t n_users, const int32_t* col_idx, int64_t n_items, const int32_t* users,
-                                     const int32_t* tests, int64_t n_rows, int32_t n_neg, int32_t* out,
-                                     int32_t* counts) {
-  HVAE_REQUIRE(mt_key && mt_pos && row_ptr && n_users >= 0 && n_items > 0 && n_items < (int64_t)1 << 31 && n_rows >= 0 &&
-                   n_neg >= 0 && n_neg <= 32767 && (n_rows == 0 || (users && tests && out && counts)),
-               "hvae_negatives_legacy: bad args (n_neg <= 32767)");
-  HVAE_REQUIRE(*mt_pos >= 0 && *mt_pos <= kMtN, "hvae_negatives_legacy: MT19937 position outside [0, 624]");
-  for (int64_t r = 0; r < n_rows; ++r) {
-    HVAE_REQUIRE(users[r] >= 0 && users[r] < n_users && tests[r] >= 0 && tests[r] < n_items,
-                 "hvae_negatives_legacy: row %lld: bad user / test item", (long long)r);
-    for (int64_t k = row_ptr[users[r]]; k < row_ptr[users[r] + 1]; ++k)
-      HVAE_REQUIRE(col_idx[k] >= 0 && col_idx[k] < n_items, "hvae_negatives_legacy: item outside [0, n_items)");
-  }
+//
+// Two callers share it. The evaluation protocol (n_draw == NULL): every row draws n_neg and writes out + r n_neg; a
+// row with fewer available items takes them all without a draw. The dataset builder (n_draw != NULL, tests may be
+// NULL): row r draws n_draw[r] <= n_neg and writes out + out_ptr[r]; its rows all have enough available items
+// (checked by the entry point before anything is drawn).
+namespace {
+int negatives_run(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_ptr, const int32_t* col_idx, int64_t n_items,
+                  const int32_t* users, const int32_t* tests, int64_t n_rows, int32_t n_neg, const int32_t* n_draw,
+                  const int64_t* out_ptr, int32_t* out, int32_t* counts) {
+  auto test_of = [&](int64_t r) { return tests ? tests[r] : (int32_t)-1; };
+  auto draws_of = [&](int64_t r) { return n_draw ? n_draw[r] : n_neg; };
   const bool avx = use_avx512();
   Mt19937 mt;
   std::memcpy(mt.key, mt_key, sizeof(mt.key));
@@ -317,9 +314,10 @@ extern "C" int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const in
       Mt19937 g;
       for (int64_t rr = wk; rr < nr; rr += kWorkers) {
         const int64_t r = c0 + rr;
-        const int32_t A = available_row(row_ptr, col_idx, n_items, users[r], tests[r], ex.data(), avail.data());
-        int32_t* o = out + r * n_neg;
-        if (As[rr] < n_neg) {  // every available item, no draw (`available if len(available) < n`)
+        const int32_t A = available_row(row_ptr, col_idx, n_items, users[r], test_of(r), ex.data(), avail.data());
+        const int32_t nd = draws_of(r);
+        int32_t* o = out_ptr ? out + out_ptr[r] : out + r * n_neg;
+        if (As[rr] < nd) {  // every available item, no draw (`available if len(available) < n`)
           std::memcpy(o, avail.data(), sizeof(int32_t) * (size_t)A);
           counts[r] = A;
           continue;
@@ -334,11 +332,11 @@ extern "C" int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const in
           draw_row_scalar<true>(g, A, js.data());
         }
         if (narrow)
-          replay_row(A, n_neg, js.data(), at8.data(), src.data());
+          replay_row(A, nd, js.data(), at8.data(), src.data());
         else
-          replay_row(A, n_neg, js.data(), at16.data(), src.data());
-        for (int32_t q = 0; q < n_neg; ++q) o[q] = avail[src[q]];
-        counts[r] = n_neg;
+          replay_row(A, nd, js.data(), at16.data(), src.data());
+        for (int32_t q = 0; q < nd; ++q) o[q] = avail[src[q]];
+        counts[r] = nd;
       }
     };
     std::vector<std::thread> th;
@@ -351,9 +349,9 @@ extern "C" int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const in
     const int64_t nr = std::min(kChunk, n_rows - c0);
     for (int64_t rr = 0; rr < nr; ++rr) {  // the stream, in row order
       const int64_t r = c0 + rr;
-      const int32_t A = available_row(row_ptr, col_idx, n_items, users[r], tests[r], ex0.data(), nullptr);
+      const int32_t A = available_row(row_ptr, col_idx, n_items, users[r], test_of(r), ex0.data(), nullptr);
       Ab[ci][rr] = A;
-      if (A < n_neg) continue;
+      if (A < draws_of(r)) continue;
       std::memcpy(snb[ci][rr].key, mt.key, sizeof(mt.key));
       snb[ci][rr].pos = mt.pos;
       if (avx)
@@ -368,6 +366,53 @@ extern "C" int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const in
   std::memcpy(mt_key, mt.key, sizeof(mt.key));
   *mt_pos = mt.pos;
   return HVAE_OK;
+}
+}  // namespace
+
+extern "C" int hvae_negatives_legacy(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_ptr,
+                                     int64_t n_users, const int32_t* col_idx, int64_t n_items, const int32_t* users,
+                                     const int32_t* tests, int64_t n_rows, int32_t n_neg, int32_t* out,
+                                     int32_t* counts) {
+  HVAE_REQUIRE(mt_key && mt_pos && row_ptr && n_users >= 0 && n_items > 0 && n_items < (int64_t)1 << 31 && n_rows >= 0 &&
+                   n_neg >= 0 && n_neg <= 32767 && (n_rows == 0 || (users && tests && out && counts)),
+               "hvae_negatives_legacy: bad args (n_neg <= 32767)");
+  HVAE_REQUIRE(*mt_pos >= 0 && *mt_pos <= kMtN, "hvae_negatives_legacy: MT19937 position outside [0, 624]");
+  for (int64_t r = 0; r < n_rows; ++r) {
+    HVAE_REQUIRE(users[r] >= 0 && users[r] < n_users && tests[r] >= 0 && tests[r] < n_items,
+                 "hvae_negatives_legacy: row %lld: bad user / test item", (long long)r);
+    for (int64_t k = row_ptr[users[r]]; k < row_ptr[users[r] + 1]; ++k)
+      HVAE_REQUIRE(col_idx[k] >= 0 && col_idx[k] < n_items, "hvae_negatives_legacy: item outside [0, n_items)");
+  }
+  return negatives_run(mt_key, mt_pos, row_ptr, col_idx, n_items, users, tests, n_rows, n_neg, nullptr, nullptr, out,
+                       counts);
+}
+
+extern "C" int hvae_negatives_legacy_rows(uint32_t* mt_key, int32_t* mt_pos, const int64_t* row_ptr, int64_t n_users,
+                                          const int32_t* col_idx, int64_t n_items, const int32_t* users,
+                                          const int32_t* tests, const int32_t* n_draw, const int64_t* out_ptr,
+                                          int64_t n_rows, int32_t* out, int32_t* counts) {
+  HVAE_REQUIRE(mt_key && mt_pos && row_ptr && n_users >= 0 && n_items > 0 && n_items < (int64_t)1 << 31 && n_rows >= 0 &&
+                   (n_rows == 0 || (users && n_draw && out_ptr && out && counts)),
+               "hvae_negatives_legacy_rows: bad args");
+  HVAE_REQUIRE(*mt_pos >= 0 && *mt_pos <= kMtN, "hvae_negatives_legacy_rows: MT19937 position outside [0, 624]");
+  int32_t most = 0;
+  std::vector<uint8_t> ex((size_t)n_items, 0);
+  for (int64_t r = 0; r < n_rows; ++r) {
+    HVAE_REQUIRE(users[r] >= 0 && users[r] < n_users && (!tests || (tests[r] >= 0 && tests[r] < n_items)),
+                 "hvae_negatives_legacy_rows: row %lld: bad user / test item", (long long)r);
+    HVAE_REQUIRE(n_draw[r] >= 0 && n_draw[r] <= 32767 && out_ptr[r] >= 0,
+                 "hvae_negatives_legacy_rows: row %lld: draw count outside [0, 32767] or negative offset", (long long)r);
+    for (int64_t k = row_ptr[users[r]]; k < row_ptr[users[r] + 1]; ++k)
+      HVAE_REQUIRE(col_idx[k] >= 0 && col_idx[k] < n_items, "hvae_negatives_legacy_rows: item outside [0, n_items)");
+    // fewer available items than draws is numpy's replace=True path (another generator call): not served
+    const int32_t A = available_row(row_ptr, col_idx, n_items, users[r], tests ? tests[r] : -1, ex.data(), nullptr);
+    if (A < n_draw[r])
+      HVAE_FAIL(HVAE_ERR_UNSUPPORTED, "hvae_negatives_legacy_rows: row %lld: %d available items for %d draws",
+                (long long)r, A, n_draw[r]);
+    most = std::max(most, n_draw[r]);
+  }
+  return negatives_run(mt_key, mt_pos, row_ptr, col_idx, n_items, users, tests, n_rows, most, n_draw, out_ptr, out,
+                       counts);
 }
 
 #endif  // __HIP_DEVICE_COMPILE__

@@ -146,6 +146,8 @@ SVD_LD = 64            # include/hvae.h HVAE_SVD_LD
 # include/hvae.h HVAE_TSNE_*: the served range of the t-SNE kernels
 TSNE_MIN_N, TSNE_MAX_N, TSNE_MIN_L, TSNE_MAX_L, TSNE_MAX_K = 33, 16384, 4, 1024, 255
 
+PREP_MAX_ID_BYTES = 32  # include/hvae.h (K23): an id is at most 4 big-endian 64-bit words
+
 P = C.POINTER
 # name ->(restype, argtypes); mirrors include/hvae.h one to one.
 SIGNATURES = {
@@ -261,6 +263,15 @@ SIGNATURES = {
     "hvae_mvae_nll": (cint, [P(CsrBatch), vp, i64, f32, vp, vp, vp]),
     "hvae_cast_bf16": (cint, [vp, vp, i64, vp]),
     "hvae_negatives_legacy": (cint, [vp, vp, vp, i64, vp, i64, vp, vp, i64, C.c_int32, vp, vp]),
+    "hvae_negatives_legacy_rows": (cint, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, vp]),
+    "hvae_prep_encode_workspace": (sz, [i64, cint]),
+    "hvae_prep_encode": (cint, [vp, i64, cint, vp, vp, vp, vp, sz, vp]),
+    "hvae_prep_kcore_workspace": (sz, [i64, i64, C.c_int32]),
+    "hvae_prep_kcore": (cint, [vp, vp, i64, i64, i64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, sz, vp]),
+    "hvae_prep_split_workspace": (sz, [i64]),
+    "hvae_prep_split": (cint, [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, sz, vp]),
+    "hvae_prep_csr_workspace": (sz, [i64, i64]),
+    "hvae_prep_csr": (cint, [vp, vp, vp, i64, i64, i64, vp, vp, vp, vp, vp, sz, vp]),
     "hvae_read_interactions": (cint, [C.c_char_p, C.c_char_p, i64, i64, C.c_char_p, i64, i64, cint,
                                       P(HostCsr)]),
     "hvae_host_csr_free": (None, [P(HostCsr)]),

@@ -542,6 +542,41 @@ def negatives_legacy(indptr, indices, n_items: int, users, tests, n_neg: int, ar
     return [out[r, :counts[r]].astype(np.int64) for r in range(R)]
 
 
+def negatives_legacy_rows(indptr, indices, n_items: int, users, n_draw, tests=None):
+    """Row r draws np.random.choice(available, n_draw[r], replace=False) from numpy's global legacy RandomState,
+    available = the items outside row users[r] of the CSR (and tests[r], when tests is given): the per-user draws of
+    DatasetBuilder.create_negative_samples (src/preprocessing/dataset.py:111-123), by the sampler of negatives_legacy
+    (hvae_negatives_legacy_rows). Returns (flat int32 draws, int64 offsets [rows + 1]). A row with fewer available
+    items than draws (numpy's replace=True path) raises RuntimeError and leaves numpy's state untouched."""
+    import numpy as np
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    users = np.ascontiguousarray(users, dtype=np.int32)
+    n_draw = np.ascontiguousarray(n_draw, dtype=np.int32)
+    if tests is not None:
+        tests = np.ascontiguousarray(tests, dtype=np.int32)
+    R = len(users)
+    if len(n_draw) != R or (tests is not None and len(tests) != R):
+        raise ValueError("negatives_legacy_rows: users, n_draw and tests must have one entry per row")
+    if R and int(n_draw.min()) < 0:
+        raise ValueError("negatives_legacy_rows: negative draw count")
+    out_ptr = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(n_draw, dtype=np.int64, out=out_ptr[1:])
+    st = np.random.get_state(legacy=True)
+    if st[0] != "MT19937":
+        raise RuntimeError(f"negatives_legacy_rows: numpy global bit generator {st[0]}, not MT19937")
+    key = np.array(st[1], dtype=np.uint32, copy=True)
+    pos = np.array([st[2]], dtype=np.int32)
+    out = np.empty(max(int(out_ptr[-1]), 1), dtype=np.int32)
+    counts = np.empty(max(R, 1), dtype=np.int32)
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    check(lib().hvae_negatives_legacy_rows(p(key), p(pos), p(indptr), len(indptr) - 1, p(indices), int(n_items),
+                                           p(users), p(tests), p(n_draw), p(out_ptr), R, p(out), p(counts)),
+          "hvae_negatives_legacy_rows")
+    np.random.set_state((st[0], key, int(pos[0]), st[3], st[4]))
+    return out[:int(out_ptr[-1])], out_ptr
+
+
 # ---------------------------------------------------------------- baselines --
 class Csc:
     """A device item-major (CSC) image of an interaction matrix: col_ptr int64 [N + 1], row_idx int32 (user ids
@@ -1285,3 +1320,148 @@ def sbert_pool_norm(x, pack: SbertPack, out=None):
     check(lib().hvae_sbert_pool_norm(ptr(x), ptr(pack.cu), pack.S, pack.T, H, ptr(out), stream_of(x)),
           "hvae_sbert_pool_norm")
     return out
+
+
+# ------------------------------------------------------- preprocessing (K23) --
+PREP_MAX_ID_BYTES = _lib.PREP_MAX_ID_BYTES
+_PREP_MAX_N = (1 << 31) - 1
+
+
+def prep_pack_ids(values, what: str = "id"):
+    """String ids -> (uint64 [n, W] host array, W): each id's UTF-8 bytes, NUL-padded to 8 W bytes (W = 1 .. 4, the
+    smallest that holds the longest id) and read as big-endian 64-bit words, the keys of hvae_prep_encode. Refused
+    with a ValueError that names the row: an id that is no str, holds a NUL, or is longer than 32 bytes of UTF-8."""
+    import numpy as np
+    objs = np.asarray(values, dtype=object)
+    if objs.ndim != 1:
+        raise ValueError(f"prep_pack_ids: {what} must be one column, got shape {objs.shape}")
+    for r, v in enumerate(objs):
+        if not isinstance(v, str):
+            raise ValueError(f"{what}: row {r}: {v!r} is {type(v).__name__}, not a string")
+        if "\x00" in v:
+            raise ValueError(f"{what}: row {r}: {v!r} contains NUL")
+    n = len(objs)
+    raw = np.char.encode(objs.astype(str), "utf-8") if n else np.zeros(0, dtype="S1")
+    width = raw.dtype.itemsize
+    if width > PREP_MAX_ID_BYTES:
+        r = int(np.argmax(np.char.str_len(raw) > PREP_MAX_ID_BYTES))
+        raise ValueError(f"{what}: row {r}: {objs[r]!r} is {len(objs[r].encode('utf-8'))} bytes of UTF-8, more than "
+                         f"the {PREP_MAX_ID_BYTES} an id may have")
+    W = max(1, -(-width // 8))
+    buf = np.zeros((n, 8 * W), dtype=np.uint8)
+    if n:
+        buf[:, :width] = np.frombuffer(raw.tobytes(), dtype=np.uint8).reshape(n, width)
+    return buf.view(">u8").astype(np.uint64), W
+
+
+def prep_unpack_ids(words) -> list[str]:
+    """The ids that prep_pack_ids packed."""
+    import numpy as np
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    rows = words.astype(">u8").view(np.uint8).reshape(len(words), -1)
+    return [bytes(r).rstrip(b"\x00").decode("utf-8") for r in rows]
+
+
+def _prep_vec(what: str, name: str, t: torch.Tensor, dtype, n: int | None = None):
+    require_hip(t)
+    if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous() or (n is not None and t.numel() != n):
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} vector" + (f" of {n}" if n is not None else "") +
+                         f", got {tuple(t.shape)} {t.dtype}")
+    if not 1 <= t.numel() <= _PREP_MAX_N:
+        raise ValueError(f"{what}: {name} holds {t.numel()} records; served: 1 .. 2^31 - 1")
+
+
+def _prep_codes(what: str, name: str, t: torch.Tensor, hi: int):
+    lo_v, hi_v = (int(x) for x in torch.aminmax(t))
+    if lo_v < 0 or hi_v >= hi:
+        raise ValueError(f"{what}: {name} must lie in [0, {hi}), got [{lo_v}, {hi_v}]")
+
+
+def _prep_ws(what: str, dev, nbytes: int) -> torch.Tensor:
+    if nbytes <= 0:
+        raise ValueError(f"{what}: sizes outside the served range (1 .. 2^31 - 1 records, users and items)")
+    ws = workspace(dev, nbytes + 256)
+    off = (-ws.data_ptr()) % 256
+    return ws[off:off + nbytes]
+
+
+def prep_encode(keys: torch.Tensor):
+    """LabelEncoder.fit + transform on packed ids (keys int64 [n, W]: the bits of prep_pack_ids' words) ->
+    (codes int32 [n], first int32 [n_classes]): each id's rank among the distinct ids in ascending byte order, and
+    the smallest record index that carries each class (hvae_prep_encode). One read-back, of the class count."""
+    require_hip(keys)
+    if keys.dtype != torch.int64 or keys.dim() != 2 or not keys.is_contiguous() or not 1 <= keys.shape[1] <= 4:
+        raise ValueError(f"prep_encode: keys must be a contiguous int64 [n, 1 .. 4] matrix, got {tuple(keys.shape)} "
+                         f"{keys.dtype}")
+    n, W = keys.shape
+    if not 1 <= n <= _PREP_MAX_N:
+        raise ValueError(f"prep_encode: {n} records; served: 1 .. 2^31 - 1")
+    dev = keys.device
+    codes = torch.empty(n, dtype=torch.int32, device=dev)
+    first = torch.empty(n, dtype=torch.int32, device=dev)
+    n_classes = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _prep_ws("prep_encode", dev, lib().hvae_prep_encode_workspace(n, W))
+    check(lib().hvae_prep_encode(ptr(keys), n, W, ptr(codes), ptr(n_classes), ptr(first), ptr(ws), ws.numel(),
+                                 stream_of(keys)), "hvae_prep_encode")
+    return codes, first[:int(n_classes.item())].clone()
+
+
+def prep_kcore(ucode: torch.Tensor, icode: torch.Tensor, n_users: int, n_items: int, min_user: int = 5,
+               min_item: int = 5, max_iterations: int = 10):
+    """filter_by_interactions over codes -> (alive bool [n], live count, rounds that removed a record)
+    (hvae_prep_kcore). All rounds are enqueued at once; the two counts are read back afterwards."""
+    _prep_vec("prep_kcore", "ucode", ucode, torch.int32)
+    n = ucode.numel()
+    _prep_vec("prep_kcore", "icode", icode, torch.int32, n)
+    _prep_codes("prep_kcore", "ucode", ucode, n_users)
+    _prep_codes("prep_kcore", "icode", icode, n_items)
+    if not 0 <= int(max_iterations) <= 1 << 20:
+        raise ValueError(f"prep_kcore: max_iterations = {max_iterations}; served: 0 .. 2^20")
+    dev = ucode.device
+    alive = torch.empty(n, dtype=torch.uint8, device=dev)
+    n_alive = torch.zeros(1, dtype=torch.int64, device=dev)
+    rounds = torch.zeros(1, dtype=torch.int32, device=dev)
+    ws = _prep_ws("prep_kcore", dev, lib().hvae_prep_kcore_workspace(n_users, n_items, int(max_iterations)))
+    clamp = lambda v: max(-(1 << 31), min(int(v), (1 << 31) - 1))  # noqa: E731
+    check(lib().hvae_prep_kcore(ptr(ucode), ptr(icode), n, n_users, n_items, clamp(min_user), clamp(min_item),
+                                int(max_iterations), ptr(alive), ptr(n_alive), ptr(rounds), ptr(ws), ws.numel(),
+                                stream_of(ucode)), "hvae_prep_kcore")
+    return alive.bool(), int(n_alive.item()), int(rounds.item())
+
+
+def prep_split(ucode: torch.Tensor, ts: torch.Tensor, n_users: int):
+    """leave_one_out_split over (user code, int64 timestamp) -> (perm, train, val, test), int32 record indices: the
+    stable (user, timestamp) order, and each part's records in that order (hvae_prep_split)."""
+    _prep_vec("prep_split", "ucode", ucode, torch.int32)
+    n = ucode.numel()
+    _prep_vec("prep_split", "ts", ts, torch.int64, n)
+    _prep_codes("prep_split", "ucode", ucode, n_users)
+    dev = ucode.device
+    perm, train, val, test = (torch.empty(n, dtype=torch.int32, device=dev) for _ in range(4))
+    lens = torch.zeros(3, dtype=torch.int64, device=dev)
+    ws = _prep_ws("prep_split", dev, lib().hvae_prep_split_workspace(n))
+    check(lib().hvae_prep_split(ptr(ucode), ptr(ts), n, n_users, ptr(perm), ptr(train), ptr(val), ptr(test),
+                                ptr(lens), ptr(ws), ws.numel(), stream_of(ucode)), "hvae_prep_split")
+    n_train, n_val, n_test = (int(x) for x in lens.tolist())
+    return perm, train[:n_train].clone(), val[:n_val].clone(), test[:n_test].clone()
+
+
+def prep_csr(ucode: torch.Tensor, icode: torch.Tensor, vals: torch.Tensor, n_users: int, n_items: int) -> Csr:
+    """create_interaction_matrix: the canonical device CSR [n_users, n_items] of all records, duplicate pairs summed
+    in input order, columns ascending, entries that sum to zero kept (hvae_prep_csr)."""
+    _prep_vec("prep_csr", "ucode", ucode, torch.int32)
+    n = ucode.numel()
+    _prep_vec("prep_csr", "icode", icode, torch.int32, n)
+    _prep_vec("prep_csr", "vals", vals, torch.float32, n)
+    _prep_codes("prep_csr", "ucode", ucode, n_users)
+    _prep_codes("prep_csr", "icode", icode, n_items)
+    dev = ucode.device
+    row_ptr = torch.empty(n_users + 1, dtype=torch.int64, device=dev)
+    col = torch.empty(n, dtype=torch.int32, device=dev)
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    nnz = torch.zeros(1, dtype=torch.int64, device=dev)
+    ws = _prep_ws("prep_csr", dev, lib().hvae_prep_csr_workspace(n, n_users))
+    check(lib().hvae_prep_csr(ptr(ucode), ptr(icode), ptr(vals), n, n_users, n_items, ptr(row_ptr), ptr(col), ptr(out),
+                              ptr(nnz), ptr(ws), ws.numel(), stream_of(ucode)), "hvae_prep_csr")
+    k = int(nnz.item())
+    return Csr(row_ptr, col[:k].clone(), out[:k].clone(), n_items)
