@@ -953,6 +953,12 @@ int hvae_tsne_update(const double* attr, const double* rep, const double* z, int
  * (dh = H / heads in {32, 64}, sequences of 1 .. 512 tokens), a streaming softmax on v_mfma_f32_16x16x4_f32. work is
  * int32 [n_work, 2]: the (sequence, 64-query chunk) pairs to compute, every chunk of every sequence once; one launch
  * of n_work x heads blocks. Rows of ctx that no work item names stay untouched; ctx may not alias qkv.
+ * hvae_sbert_attention_relbias (MPNet bodies): the same with a learned relative-position bias per head,
+ * ctx = softmax(Q K^T / sqrt(dh) + bias) V, the bias added after the scale. rel is fp32 [heads, 2 L - 1] and
+ * rel[h][(j - i) + L - 1] is the bias of key j for query i in head h; 1 <= L <= 512 is the longest sequence the table
+ * covers. Each block stages its window of the head's row (at most 575 deltas) into LDS once; nothing outside rel is
+ * read. A sequence longer than L leaves its rows untouched. Work list, packing, summation order and the untouched
+ * rows are hvae_sbert_attention's, whose kernels are unchanged; with an all-zero rel the result is bitwise its.
  * hvae_sbert_pool_norm: out[s] = mean of x's rows cu[s] .. cu[s + 1] - 1, divided by max(its L2 norm, 1e-12), [S, H].
  */
 int hvae_sbert_supported(int64_t H, int64_t heads, int64_t max_len);
@@ -963,6 +969,9 @@ int hvae_sbert_add_ln(const float* x, const float* res, const float* ln_w, const
                       int64_t H, float* out, void* stream);
 int hvae_sbert_attention(const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H, int64_t heads,
                          const int32_t* work, int64_t n_work, float* ctx, void* stream);
+int hvae_sbert_attention_relbias(const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H, int64_t heads,
+                                 const int32_t* work, int64_t n_work, const float* rel, int64_t L, float* ctx,
+                                 void* stream);
 int hvae_sbert_pool_norm(const float* x, const int32_t* cu, int64_t S, int64_t T, int64_t H, float* out,
                          void* stream);
 

@@ -23,6 +23,7 @@ constexpr int kSbRowF4 = kSbMaxH / 4 / 64;
 constexpr int kSbTK = 16;           // keys per K / V tile
 constexpr int kSbQW = 16;           // queries per wave
 constexpr int kSbQB = 64;           // queries per block: one work item
+constexpr int kSbRelN = kSbMaxLen + kSbQB;  // a chunk's relative-bias window: at most 575 deltas, rounded up
 
 // ---- LayerNorm over one row held by one wave -----------------------------------------------------------------
 // Lane l holds the float4 columns l, l + 64, ... (at most kSbRowF4). mean = sum / H and var = sum (x - mean)^2 / H
@@ -135,10 +136,20 @@ __global__ void __launch_bounds__(256) k_sbert_add_ln(const float* x, const floa
 // Keys past the sequence's end score -inf (their V rows are staged as zeros). Query rows past the end load zeros
 // and are never stored: in the packed layout they are the next sequence's tokens. The sums over keys run in tile
 // order; inside a tile the MFMA's k order, then the xor butterfly over the four lane groups.
-template <int DH>
+//
+// BIAS (MPNet's relative-position bias): score (query i, key j) += rel[head][(j - i) + L - 1], rel [heads, 2 L - 1],
+// after the scale. A chunk's queries c 64 .. c 64 + 63 against keys 0 .. 16 ntiles - 1 need the deltas
+// -(c 64 + 63) .. 16 ntiles - 1 - c 64: that window of the head's row is staged once into relw, relw[x] = the bias
+// of delta x - (c 64 + 63), before the first barrier. An entry outside the table is staged as 0: it belongs to a
+// query or a key past the sequence's end (len <= L), whose score is never stored or is -inf. Lane (q, c16) of wave w
+// reads relw[63 + 4 q - 16 w - c16 + 16 t + r], r = 0 .. 3: the 32 lanes of a ds_read_b32 group span 20 consecutive
+// floats, so lanes either share an address (broadcast) or hit distinct banks. Without BIAS rel and L are not read
+// and relw is not allocated.
+template <int DH, bool BIAS>
 __global__ void __launch_bounds__(256) k_sbert_attn(const float* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                     int S, int T, int H, const int32_t* __restrict__ work,
-                                                    float scale, float* __restrict__ ctx) {
+                                                    float scale, float* __restrict__ ctx,
+                                                    const float* __restrict__ rel, int L) {
   constexpr int KS = DH / 4;
   constexpr int DB = DH / 16;
   constexpr int LD = DH + 4;
@@ -147,6 +158,7 @@ __global__ void __launch_bounds__(256) k_sbert_attn(const float* __restrict__ qk
   constexpr int LPT = 2 * kSbTK * Q4 / 256;
   static_assert(LPT * 256 == 2 * kSbTK * Q4, "the K and V tiles are a whole number of float4 per thread");
   __shared__ __attribute__((aligned(16))) float lds[2][2 * TF];
+  __shared__ float relw[BIAS ? kSbRelN : 1];
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, q = lane >> 4, c16 = lane & 15;
   const int seq = work[2 * blockIdx.x], chunk = work[2 * blockIdx.x + 1];
@@ -154,6 +166,7 @@ __global__ void __launch_bounds__(256) k_sbert_attn(const float* __restrict__ qk
   const int base = cu[seq], len = cu[seq + 1] - base;
   if (base < 0 || len <= 0 || len > kSbMaxLen || base + len > T) return;
   if (chunk < 0 || chunk * kSbQB >= len) return;
+  if (BIAS && len > L) return;  // the table does not cover the sequence: untouched rows
   const int head = blockIdx.y;
   const int ld3 = 3 * H;
   const float* qkv_s = qkv + (int64_t)base * ld3 + head * DH;
@@ -191,6 +204,15 @@ __global__ void __launch_bounds__(256) k_sbert_attn(const float* __restrict__ qk
   };
 
   const int ntiles = (len + kSbTK - 1) / kSbTK;
+  if constexpr (BIAS) {
+    const float* relh = rel + (int64_t)head * (2 * L - 1);
+    const int g0 = L - 1 - (chunk * kSbQB + kSbQB - 1);  // the table index of relw[0]
+    for (int x = tid; x < ntiles * kSbTK + kSbQB; x += 256) {  // at most 512 + 64 = kSbRelN
+      const int g = g0 + x;
+      relw[x] = (g >= 0 && g <= 2 * L - 2) ? relh[g] : 0.f;
+    }
+  }
+  const int rb = kSbQB - 1 + 4 * q - kSbQW * w - c16;  // 0 .. 75; + 16 t + r <= 574
   gload(0);
   lstore(lds[0]);
   __syncthreads();
@@ -212,7 +234,10 @@ __global__ void __launch_bounds__(256) k_sbert_attn(const float* __restrict__ qk
       float mx = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        sc[r] = (kbase + r < len) ? (s0[r] + s1[r]) * scale : -INFINITY;
+        if constexpr (BIAS)
+          sc[r] = (kbase + r < len) ? (s0[r] + s1[r]) * scale + relw[rb + t * kSbTK + r] : -INFINITY;
+        else
+          sc[r] = (kbase + r < len) ? (s0[r] + s1[r]) * scale : -INFINITY;
         mx = fmaxf(mx, sc[r]);
       }
       mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -359,26 +384,45 @@ extern "C" int hvae_sbert_add_ln(const float* x, const float* res, const float* 
   return HVAE_OK;
 }
 
-extern "C" int hvae_sbert_attention(const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H,
-                                    int64_t heads, const int32_t* work, int64_t n_work, float* ctx, void* stream) {
+// The two attention entry points share their checks and launch; fn names the caller in the messages.
+template <bool BIAS>
+static int sbert_attention_launch(const char* fn, const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H,
+                                  int64_t heads, const int32_t* work, int64_t n_work, const float* rel, int64_t L,
+                                  float* ctx, void* stream) {
   HVAE_REQUIRE(hvae_sbert_supported(H, heads, 1),
-               "hvae_sbert_attention: H = %lld with %lld heads is not served (head width 32 or 64, H <= %d)",
-               (long long)H, (long long)heads, kSbMaxH);
-  HVAE_REQUIRE(S >= 1 && T >= 1 && S <= T && T < (1LL << 31) / (3 * H), "hvae_sbert_attention: S = %lld, T = %lld",
-               (long long)S, (long long)T);
-  HVAE_REQUIRE(n_work >= 1 && n_work < (1LL << 31) && heads <= 65535, "hvae_sbert_attention: n_work = %lld",
-               (long long)n_work);
-  HVAE_REQUIRE(qkv && cu && work && ctx && qkv != ctx, "hvae_sbert_attention: null or aliased pointer");
-  HVAE_REQUIRE(al16(qkv) && al16(ctx), "hvae_sbert_attention: qkv and ctx must be 16-byte aligned");
+               "%s: H = %lld with %lld heads is not served (head width 32 or 64, H <= %d)", fn, (long long)H,
+               (long long)heads, kSbMaxH);
+  HVAE_REQUIRE(S >= 1 && T >= 1 && S <= T && T < (1LL << 31) / (3 * H), "%s: S = %lld, T = %lld", fn, (long long)S,
+               (long long)T);
+  HVAE_REQUIRE(n_work >= 1 && n_work < (1LL << 31) && heads <= 65535, "%s: n_work = %lld", fn, (long long)n_work);
+  HVAE_REQUIRE(!BIAS || (L >= 1 && L <= kSbMaxLen), "%s: L = %lld is not served (1 .. %d)", fn, (long long)L,
+               kSbMaxLen);
+  HVAE_REQUIRE(qkv && cu && work && ctx && qkv != ctx && (!BIAS || rel), "%s: null or aliased pointer", fn);
+  HVAE_REQUIRE(al16(qkv) && al16(ctx), "%s: qkv and ctx must be 16-byte aligned", fn);
   const int64_t dh = H / heads;
   const float scale = (float)(1.0 / sqrt((double)dh));
   const dim3 grid((unsigned)n_work, (unsigned)heads);
   if (dh == 32)
-    k_sbert_attn<32><<<grid, 256, 0, as_stream(stream)>>>(qkv, cu, (int)S, (int)T, (int)H, work, scale, ctx);
+    k_sbert_attn<32, BIAS><<<grid, 256, 0, as_stream(stream)>>>(qkv, cu, (int)S, (int)T, (int)H, work, scale, ctx,
+                                                                rel, (int)L);
   else
-    k_sbert_attn<64><<<grid, 256, 0, as_stream(stream)>>>(qkv, cu, (int)S, (int)T, (int)H, work, scale, ctx);
+    k_sbert_attn<64, BIAS><<<grid, 256, 0, as_stream(stream)>>>(qkv, cu, (int)S, (int)T, (int)H, work, scale, ctx,
+                                                                rel, (int)L);
   HVAE_LAUNCH_CHECK("k_sbert_attn");
   return HVAE_OK;
+}
+
+extern "C" int hvae_sbert_attention(const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H,
+                                    int64_t heads, const int32_t* work, int64_t n_work, float* ctx, void* stream) {
+  return sbert_attention_launch<false>("hvae_sbert_attention", qkv, cu, S, T, H, heads, work, n_work, nullptr, 0, ctx,
+                                       stream);
+}
+
+extern "C" int hvae_sbert_attention_relbias(const float* qkv, const int32_t* cu, int64_t S, int64_t T, int64_t H,
+                                            int64_t heads, const int32_t* work, int64_t n_work, const float* rel,
+                                            int64_t L, float* ctx, void* stream) {
+  return sbert_attention_launch<true>("hvae_sbert_attention_relbias", qkv, cu, S, T, H, heads, work, n_work, rel, L,
+                                      ctx, stream);
 }
 
 extern "C" int hvae_sbert_pool_norm(const float* x, const int32_t* cu, int64_t S, int64_t T, int64_t H, float* out,

@@ -256,6 +256,7 @@ SIGNATURES = {
     "hvae_sbert_embed_ln": (cint, [vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, f32, i64, vp, vp]),
     "hvae_sbert_add_ln": (cint, [vp, vp, vp, vp, f32, i64, i64, vp, vp]),
     "hvae_sbert_attention": (cint, [vp, vp, i64, i64, i64, i64, vp, i64, vp, vp]),
+    "hvae_sbert_attention_relbias": (cint, [vp, vp, i64, i64, i64, i64, vp, i64, vp, i64, vp, vp]),
     "hvae_sbert_pool_norm": (cint, [vp, vp, i64, i64, i64, vp, vp]),
     "hvae_mvae_encoder_fwd": (cint, [P(CsrBatch), vp, vp, i64, f32, f32, vp, vp, u64, vp, cint, vp, vp, vp, vp]),
     "hvae_mvae_tanh_drop_fwd": (cint, [vp, i64, i64, i64, f32, vp, u64, vp, u32, cint, vp, vp, i64, vp]),

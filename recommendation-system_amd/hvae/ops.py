@@ -1287,10 +1287,16 @@ def sbert_add_ln(x, res, ln_w, ln_b, eps: float, out=None):
     return out
 
 
-def sbert_attention(qkv, pack: SbertPack, heads: int, ctx=None):
+def sbert_attention(qkv, pack: SbertPack, heads: int, ctx=None, rel=None, rel_len=None):
     """ctx [T, H] = softmax(Q K^T / sqrt(dh)) V inside each sequence and head, from qkv [T, 3 H]
-    (hvae_sbert_attention). ctx may have more than T rows: rows from T on are not touched."""
+    (hvae_sbert_attention). ctx may have more than T rows: rows from T on are not touched.
+
+    With rel, a float32 [heads, 2 L - 1] table (L = rel_len, 1 .. 512), score (query i, key j) of head h gets
+    rel[h][(j - i) + L - 1] added after the scale (hvae_sbert_attention_relbias, MPNet's relative-position bias). The
+    device leaves a sequence longer than L untouched and cannot report it, so a pack that holds one is refused here."""
     what = "sbert_attention"
+    if (rel is None) != (rel_len is None):
+        raise ValueError(f"{what}: rel and rel_len are given together or not at all")
     if qkv.dim() != 2 or qkv.shape[1] % 3:
         raise ValueError(f"{what}: qkv must be a float32 [T, 3 H] matrix, got {tuple(qkv.shape)}")
     H = qkv.shape[1] // 3
@@ -1302,6 +1308,21 @@ def sbert_attention(qkv, pack: SbertPack, heads: int, ctx=None):
     if ctx.dim() != 2 or ctx.shape[0] < pack.T:
         raise ValueError(f"{what}: ctx needs at least {pack.T} rows")
     _sbert_mat(what, "ctx", ctx, ctx.shape[0], H)
+    if rel is not None:
+        L = int(rel_len)
+        if L < 1 or L > SBERT_MAX_LEN:
+            raise ValueError(f"{what}: rel_len = {L} is not served (1 .. {SBERT_MAX_LEN})")
+        require_hip(rel)
+        if rel.dtype != torch.float32 or tuple(rel.shape) != (int(heads), 2 * L - 1) or not rel.is_contiguous():
+            raise ValueError(f"{what}: rel must be a contiguous float32 [{int(heads)}, {2 * L - 1}] matrix (heads, "
+                             f"2 rel_len - 1), got {tuple(rel.shape)} {rel.dtype} with strides {tuple(rel.stride())}")
+        if pack.max_len > L:
+            raise ValueError(f"{what}: a sequence of {pack.max_len} tokens is longer than the relative-bias table "
+                             f"covers (rel_len = {L})")
+        check(lib().hvae_sbert_attention_relbias(ptr(qkv), ptr(pack.cu), pack.S, pack.T, H, int(heads),
+                                                 ptr(pack.work), pack.n_work, ptr(rel), L, ptr(ctx),
+                                                 stream_of(qkv)), "hvae_sbert_attention_relbias")
+        return ctx
     check(lib().hvae_sbert_attention(ptr(qkv), ptr(pack.cu), pack.S, pack.T, H, int(heads), ptr(pack.work),
                                      pack.n_work, ptr(ctx), stream_of(qkv)), "hvae_sbert_attention")
     return ctx

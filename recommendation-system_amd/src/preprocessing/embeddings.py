@@ -7,7 +7,8 @@ Mirrors src/preprocessing/embeddings.py of the reference: ItemEmbeddingGenerator
 
 The reference hands the model name to SentenceTransformer, which fetches it. Here nothing is fetched: model_name is a
 model directory, or the name of one under config.SBERT_MODEL_DIR, and the encoder is src/preprocessing/sbert.py on
-the K22 kernels (BERT-family models only; anything else is refused by name).
+the K22 kernels (BERT and MPNet bodies, such as all-MiniLM-L6-v2 and all-mpnet-base-v2; anything else is refused by
+name).
 """
 from __future__ import annotations
 

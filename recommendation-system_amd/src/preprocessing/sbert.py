@@ -1,7 +1,9 @@
 """A BERT-family sentence encoder on the device: what SentenceTransformer(model_dir).encode(texts,
 normalize_embeddings=True) computes for a model such as all-MiniLM-L6-v2 (src/preprocessing/embeddings.py:35-63 of the
 reference), from a local model directory and without transformers, tokenizers, sentence_transformers,
-huggingface_hub or safetensors.
+huggingface_hub or safetensors. Two bodies are served: BertModel (model_type "bert") and MPNetModel ("mpnet", as in
+all-mpnet-base-v2): the same post-LayerNorm layers with a learned relative-position bias on every attention score,
+positions that start at 2, no token types, and <s> ... </s> around the pieces.
 
   load_model_dir(path)   config.json, model.safetensors | pytorch_model.bin, vocab.txt and the optional
                          sentence-transformers files -> SbertModel (fp32 numpy weights, the vocabulary, the limits)
@@ -23,17 +25,52 @@ from pathlib import Path
 
 import numpy as np
 
-SPECIAL_TOKENS = ("[UNK]", "[SEP]", "[PAD]", "[CLS]", "[MASK]")
 MAX_WORD_CHARS = 100  # WordPiece's max_input_chars_per_word
 IGNORED_TENSORS = ("pooler.", "embeddings.position_ids")
+SERVED_MODEL_TYPES = ("bert", "mpnet")
+# the special tokens by model type: BertTokenizer's and MPNetTokenizer's defaults
+SPECIALS = {"bert": {"cls_token": "[CLS]", "sep_token": "[SEP]", "pad_token": "[PAD]", "mask_token": "[MASK]",
+                     "unk_token": "[UNK]"},
+            "mpnet": {"cls_token": "<s>", "sep_token": "</s>", "pad_token": "<pad>", "mask_token": "<mask>",
+                      "unk_token": "[UNK]"}}
+# the layer tensors by model type: query, key, value, attention output, the LayerNorm after it
+LAYER_NAMES = {"bert": ("attention.self.query", "attention.self.key", "attention.self.value",
+                        "attention.output.dense", "attention.output.LayerNorm"),
+               "mpnet": ("attention.attn.q", "attention.attn.k", "attention.attn.v", "attention.attn.o",
+                         "attention.LayerNorm")}
+REL_BIAS = "encoder.relative_attention_bias.weight"  # MPNet's [32, heads] table, shared by all layers
+REL_BUCKETS, REL_MAX_DISTANCE = 32, 128  # MPNetEncoder.compute_position_bias's arguments; not read from the config
+MPNET_POS_OFFSET = 2  # MPNet's positions start at padding_idx + 1
 
 
 # ------------------------------------------------------------------------------------------------ weights ----
-def _tensor_name(name: str) -> str | None:
-    """BertModel's name of a checkpoint tensor (an optional "bert." prefix dropped), or None for one the encoder
-    does not read: pooler.* and embeddings.position_ids (an int64 buffer in real checkpoints)."""
-    name = name[5:] if name.startswith("bert.") else name
+def _tensor_name(name: str, model_type: str = "bert") -> str | None:
+    """The model's own name of a checkpoint tensor (an optional "bert." / "mpnet." prefix dropped), or None for one
+    the encoder does not read: pooler.* and embeddings.position_ids (an int64 buffer in real checkpoints)."""
+    prefix = model_type + "."
+    name = name[len(prefix):] if name.startswith(prefix) else name
     return None if name.startswith(IGNORED_TENSORS) else name
+
+
+def relative_position_bucket(delta) -> np.ndarray:
+    """MPNetEncoder.relative_position_bucket (T5's rule, 32 buckets, max_distance 128) of delta = key - query: with
+    n = -delta, 16 [n < 0] + (|n| if |n| < 8 else min(15, 8 + floor(log(|n| / 8) / log(16) * 8)))."""
+    n = -np.asarray(delta, dtype=np.int64)
+    half, exact = REL_BUCKETS // 2, REL_BUCKETS // 4
+    a = np.abs(n)
+    large = exact + (np.log(np.maximum(a, 1) / exact) / np.log(REL_MAX_DISTANCE / exact) * (half - exact)).astype(
+        np.int64)
+    return (n < 0) * half + np.where(a < exact, a, np.minimum(large, half - 1))
+
+
+def relative_bias_table(weight: np.ndarray, L: int) -> np.ndarray:
+    """rel [heads, 2 L - 1] float32 from MPNet's [32, heads] weight: rel[h][(j - i) + L - 1] is the bias of key j for
+    query i, for sequences of up to L tokens (hvae_sbert_attention_relbias's table)."""
+    weight = np.asarray(weight)
+    if weight.ndim != 2 or weight.shape[0] != REL_BUCKETS or L < 1:
+        raise ValueError(f"relative_bias_table: weight {weight.shape} must be [{REL_BUCKETS}, heads] and L = {L} >= 1")
+    bucket = relative_position_bucket(np.arange(-(L - 1), L))
+    return np.ascontiguousarray(weight[bucket].T, dtype=np.float32)
 
 
 def read_safetensors(path, rename=lambda name: name) -> dict[str, np.ndarray]:
@@ -101,9 +138,12 @@ class SbertModel:
     lower_text: bool             # sentence_bert_config.json's: lower-case the text before tokenising
     vocab: list[str] = field(repr=False)
     tensors: dict[str, np.ndarray] = field(repr=False)
+    model_type: str = "bert"
+    special_tokens: dict[str, str] | None = None  # cls_token, sep_token, ...; None: the model type's defaults
 
     def tokenizer(self) -> "WordPieceTokenizer":
-        return WordPieceTokenizer(self.vocab, self.do_lower_case, self.max_seq_length, self.lower_text)
+        return WordPieceTokenizer(self.vocab, self.do_lower_case, self.max_seq_length, self.lower_text,
+                                  **{**SPECIALS[self.model_type], **(self.special_tokens or {})})
 
 
 def _read_json(p: Path) -> dict | list | None:
@@ -111,14 +151,24 @@ def _read_json(p: Path) -> dict | list | None:
 
 
 def load_model_dir(path) -> SbertModel:
-    """Read a sentence-transformers / BertModel directory. Anything this encoder does not compute is refused with an
-    error that names the field."""
+    """Read a sentence-transformers / BertModel or MPNetModel directory. Anything this encoder does not compute is
+    refused with an error that names the field."""
     path = Path(path)
     cfg = _read_json(path / "config.json")
     if cfg is None:
         raise FileNotFoundError(f"{path}: config.json not found")
-    if cfg.get("model_type") != "bert":
-        raise ValueError(f"{path}/config.json: model_type = {cfg.get('model_type')!r}; only 'bert' is served")
+    mtype = cfg.get("model_type")
+    if mtype not in SERVED_MODEL_TYPES:
+        raise ValueError(f"{path}/config.json: model_type = {mtype!r}; only "
+                         f"{' and '.join(repr(t) for t in SERVED_MODEL_TYPES)} are served")
+    mpnet = mtype == "mpnet"
+    if mpnet and cfg.get("relative_attention_num_buckets", REL_BUCKETS) != REL_BUCKETS:
+        raise ValueError(f"{path}/config.json: relative_attention_num_buckets = "
+                         f"{cfg['relative_attention_num_buckets']!r}; only {REL_BUCKETS} is served (MPNetModel itself "
+                         "computes its buckets with 32 whatever the config says)")
+    if mpnet and cfg.get("pad_token_id", 1) != 1:
+        raise ValueError(f"{path}/config.json: pad_token_id = {cfg['pad_token_id']!r} with model_type = {mtype!r}; "
+                         f"only 1 is served (MPNet's positions start at pad_token_id + 1 = {MPNET_POS_OFFSET})")
     if cfg.get("position_embedding_type", "absolute") != "absolute":
         raise ValueError(f"{path}/config.json: position_embedding_type = {cfg['position_embedding_type']!r}; only "
                          "'absolute' is served")
@@ -156,9 +206,18 @@ def load_model_dir(path) -> SbertModel:
     if not tk.get("tokenize_chinese_chars", True):
         raise ValueError(f"{path}/tokenizer_config.json: tokenize_chinese_chars = false is not served")
     max_seq = sb.get("max_seq_length") or tk.get("model_max_length") or max_pos
-    max_seq = int(min(max_seq, max_pos))
+    max_seq = int(min(max_seq, max_pos - MPNET_POS_OFFSET if mpnet else max_pos))
     if max_seq < 3:
         raise ValueError(f"{path}: max_seq_length = {max_seq} leaves no room for a token between [CLS] and [SEP]")
+    specials = None
+    if mpnet:  # tokenizer_config.json wins over special_tokens_map.json, as in transformers
+        specials = dict(SPECIALS[mtype])
+        for source in (_read_json(path / "special_tokens_map.json") or {}, tk):
+            for key in specials:
+                v = source.get(key)
+                v = v.get("content") if isinstance(v, dict) else v
+                if isinstance(v, str):
+                    specials[key] = v
 
     from hvae import _lib
     if not _lib.lib().hvae_sbert_supported(H, heads, max_seq):
@@ -168,25 +227,39 @@ def load_model_dir(path) -> SbertModel:
     if inter % 4:
         raise ValueError(f"{path}/config.json: intermediate_size = {inter} must be a multiple of 4")
 
+    rename = lambda name: _tensor_name(name, mtype)  # noqa: E731
     if (path / "model.safetensors").exists():
-        raw = read_safetensors(path / "model.safetensors", _tensor_name)
+        raw = read_safetensors(path / "model.safetensors", rename)
     elif (path / "pytorch_model.bin").exists():
-        raw = read_torch_bin(path / "pytorch_model.bin", _tensor_name)
+        raw = read_torch_bin(path / "pytorch_model.bin", rename)
     else:
         raise FileNotFoundError(f"{path}: neither model.safetensors nor pytorch_model.bin found")
     tensors = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in raw.items()}
     want = {"embeddings.word_embeddings.weight": None, "embeddings.position_embeddings.weight": (max_pos, H),
             "embeddings.token_type_embeddings.weight": None, "embeddings.LayerNorm.weight": (H,),
             "embeddings.LayerNorm.bias": (H,)}
-    linear = {"attention.self.query": (H, H), "attention.self.key": (H, H), "attention.self.value": (H, H),
-              "attention.output.dense": (H, H), "intermediate.dense": (inter, H), "output.dense": (H, inter)}
+    if mpnet:
+        del want["embeddings.token_type_embeddings.weight"]
+    nq, nk, nv, no, nln = LAYER_NAMES[mtype]
+    linear = {nq: (H, H), nk: (H, H), nv: (H, H), no: (H, H), "intermediate.dense": (inter, H),
+              "output.dense": (H, inter)}
     for i in range(layers):
         p = f"encoder.layer.{i}."
         for n, (out_f, in_f) in linear.items():
             want[p + n + ".weight"], want[p + n + ".bias"] = (out_f, in_f), (out_f,)
-        for n in ("attention.output.LayerNorm", "output.LayerNorm"):
+        for n in (nln, "output.LayerNorm"):
             want[p + n + ".weight"], want[p + n + ".bias"] = (H,), (H,)
+    if mpnet:
+        want[REL_BIAS] = (REL_BUCKETS, heads)
     for n, shape in want.items():
+        if mpnet:  # the state dict follows the config's model_type: name it, a BERT checkpoint has other names
+            if n not in tensors:
+                raise ValueError(f"{path}: model_type = {mtype!r} expects tensor {n!r}, which is missing from the "
+                                 "weights")
+            if shape is not None and tuple(tensors[n].shape) != shape:
+                raise ValueError(f"{path}: model_type = {mtype!r} expects tensor {n!r} of shape {shape}, it has "
+                                 f"{tuple(tensors[n].shape)}")
+            continue
         if n not in tensors:
             raise ValueError(f"{path}: tensor {n!r} is missing from the weights")
         if shape is not None and tuple(tensors[n].shape) != shape:
@@ -203,13 +276,15 @@ def load_model_dir(path) -> SbertModel:
     if word.ndim != 2 or word.shape[1] != H or word.shape[0] < len(vocab):
         raise ValueError(f"{path}: tensor 'embeddings.word_embeddings.weight' has shape {tuple(word.shape)}; vocab.txt "
                          f"holds {len(vocab)} pieces of width {H}")
-    tt = tensors["embeddings.token_type_embeddings.weight"]
-    if tt.ndim != 2 or tt.shape[1] != H or tt.shape[0] < 1:
-        raise ValueError(f"{path}: tensor 'embeddings.token_type_embeddings.weight' has shape {tuple(tt.shape)}")
+    if not mpnet:
+        tt = tensors["embeddings.token_type_embeddings.weight"]
+        if tt.ndim != 2 or tt.shape[1] != H or tt.shape[0] < 1:
+            raise ValueError(f"{path}: tensor 'embeddings.token_type_embeddings.weight' has shape {tuple(tt.shape)}")
     return SbertModel(path=path, hidden_size=H, heads=heads, layers=layers, intermediate_size=inter,
                       max_position=max_pos, layer_norm_eps=float(cfg.get("layer_norm_eps", 1e-12)),
                       max_seq_length=max_seq, do_lower_case=lower,
-                      lower_text=bool(sb.get("do_lower_case", False)), vocab=vocab, tensors=tensors)
+                      lower_text=bool(sb.get("do_lower_case", False)), vocab=vocab, tensors=tensors,
+                      model_type=mtype, special_tokens=specials)
 
 
 # ---------------------------------------------------------------------------------------------- tokenizer ----
@@ -235,19 +310,22 @@ def _is_cjk(cp: int) -> bool:
 
 
 class WordPieceTokenizer:
-    """BertTokenizer restated. encode(text) -> [CLS] pieces [SEP] as vocabulary ids, at most max_seq_length."""
+    """BertTokenizer restated. encode(text) -> [CLS] pieces [SEP] as vocabulary ids, at most max_seq_length. The
+    special tokens default to BertTokenizer's; MPNetTokenizer is the same WordPiece with SPECIALS["mpnet"]."""
 
     def __init__(self, vocab: list[str], do_lower_case: bool = True, max_seq_length: int = 512,
-                 lower_text: bool = False):
+                 lower_text: bool = False, cls_token: str = "[CLS]", sep_token: str = "[SEP]",
+                 pad_token: str = "[PAD]", mask_token: str = "[MASK]", unk_token: str = "[UNK]"):
         self.ids = {}
         for i, piece in enumerate(vocab):
             self.ids.setdefault(piece, i)
-        for t in ("[UNK]", "[CLS]", "[SEP]"):
+        for t in (unk_token, cls_token, sep_token):
             if t not in self.ids:
                 raise ValueError(f"vocab.txt: the special token {t} is missing")
-        self.unk, self.cls, self.sep = self.ids["[UNK]"], self.ids["[CLS]"], self.ids["[SEP]"]
+        self.unk, self.cls, self.sep = self.ids[unk_token], self.ids[cls_token], self.ids[sep_token]
         self.do_lower_case, self.max_seq_length, self.lower_text = do_lower_case, int(max_seq_length), lower_text
-        specials = [t for t in SPECIAL_TOKENS if t in self.ids]
+        specials = [t for t in dict.fromkeys((unk_token, sep_token, pad_token, cls_token, mask_token))
+                    if t in self.ids]
         self._special = re.compile("(" + "|".join(re.escape(t) for t in sorted(specials, key=len, reverse=True)) + ")")
         self._cache: dict[str, list[int]] = {}
 
@@ -334,18 +412,26 @@ class SbertEncoder:
         t = model.tensors
         up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32), device=self.device)  # noqa: E731
         self.word = up(t["embeddings.word_embeddings.weight"])
-        self.pos = up(t["embeddings.position_embeddings.weight"])
-        self.type0 = up(t["embeddings.token_type_embeddings.weight"][0])
+        if model.model_type == "mpnet":
+            # position t of a sequence reads the table's row t + 2; no token types: an exact zero changes no sum's bits
+            self.pos = up(t["embeddings.position_embeddings.weight"][MPNET_POS_OFFSET:])
+            self.type0 = torch.zeros(model.hidden_size, device=self.device)
+            self.rel_len = model.max_seq_length
+            self.rel = up(relative_bias_table(t[REL_BIAS], self.rel_len))
+        else:
+            self.pos = up(t["embeddings.position_embeddings.weight"])
+            self.type0 = up(t["embeddings.token_type_embeddings.weight"][0])
+            self.rel, self.rel_len = None, None
         self.emb_ln = (up(t["embeddings.LayerNorm.weight"]), up(t["embeddings.LayerNorm.bias"]))
+        nq, nk, nv, no, nln = LAYER_NAMES[model.model_type]
         self.layers = []
         for i in range(model.layers):
             p = f"encoder.layer.{i}."
-            sa = p + "attention.self."
             self.layers.append({
-                "wqkv": up(np.concatenate([t[sa + n + ".weight"] for n in ("query", "key", "value")], axis=0)),
-                "bqkv": up(np.concatenate([t[sa + n + ".bias"] for n in ("query", "key", "value")], axis=0)),
-                "wo": up(t[p + "attention.output.dense.weight"]), "bo": up(t[p + "attention.output.dense.bias"]),
-                "ln1": (up(t[p + "attention.output.LayerNorm.weight"]), up(t[p + "attention.output.LayerNorm.bias"])),
+                "wqkv": up(np.concatenate([t[p + n + ".weight"] for n in (nq, nk, nv)], axis=0)),
+                "bqkv": up(np.concatenate([t[p + n + ".bias"] for n in (nq, nk, nv)], axis=0)),
+                "wo": up(t[p + no + ".weight"]), "bo": up(t[p + no + ".bias"]),
+                "ln1": (up(t[p + nln + ".weight"]), up(t[p + nln + ".bias"])),
                 "wi": up(t[p + "intermediate.dense.weight"]), "bi": up(t[p + "intermediate.dense.bias"]),
                 "wd": up(t[p + "output.dense.weight"]), "bd": up(t[p + "output.dense.bias"]),
                 "ln2": (up(t[p + "output.LayerNorm.weight"]), up(t[p + "output.LayerNorm.bias"])),
@@ -384,7 +470,10 @@ class SbertEncoder:
         pre = torch.empty(T, m.intermediate_size, device=self.device)
         for L in self.layers:
             self._stage("qkv", lambda: ops.gemm(x, L["wqkv"].t(), out=qkv, epi=bias(L["bqkv"])))
-            self._stage("attention", lambda: ops.sbert_attention(qkv, pack, heads, ctx))
+            if self.rel is None:
+                self._stage("attention", lambda: ops.sbert_attention(qkv, pack, heads, ctx))
+            else:
+                self._stage("attention", lambda: ops.sbert_attention(qkv, pack, heads, ctx, self.rel, self.rel_len))
 
             def output():
                 ops.gemm(ctx, L["wo"].t(), out=a, epi=bias(L["bo"]))
